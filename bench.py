@@ -14,13 +14,16 @@ frame: SURVEY 8e); RCCL is used only for the timing barrier / max-over-ranks. In
 HBM when the timed region starts; each step ends with the one D2H of its final boxes / scores /
 labels into host memory (inside the timed region; --device-results leaves them in HBM).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...). A plain run
+does nothing else: set up, warm up, time --steps steps, write the last timed step's outputs if --dump-outputs DIR is given, print.
+With --full the line also carries everything else the bench measures and checks:
+  results_digest: every timed step's detections digested and compared with the same steps re-run on one stream (exit 1 if they differ)
   roofline     : the dominant conv kernel (today window_conv_f16_kernel<128>: split-fp16 on the fp16 MFMA pipe, priced against
                  2500 / 3 TFLOP/s) measured live with HIP events on the launch stream in a second pass right after the timed
                  region; `traffic` from the round's committed rocprofv3 --pmc passes of this same command
   cpu_baseline : the CPU oracle (oracle/, a port of the reference algorithm) timed on this box's host cores: median of five
                  full frames on all hardware threads, and one frame on ONE thread (rank 0, N = 1 only)
-and, at N = 1 unless --no-extras, measured in the same process right after the timed region (each its own engine, same clouds):
+and, at N = 1 with --full unless --no-extras, measured in the same process right after the timed region (each its own engine, same clouds):
   value_fp32_mfma      frames/s of the same step with conv_math = "f32" (fp32-input MFMA everywhere: the reference's arithmetic)
   value_batch4         frames/s at the reference's eval batch (4 frames per step, voxel_rcnn_cproto_center.yaml:188)
   latency_1frame_ms    one frame per step
@@ -97,11 +100,20 @@ def parse():
                     "workspace each): the latency-bound sparse kernels of one batch overlap the matrix-bound dense ones of the other "
                     "(1 -> 2 streams: +3.2 %%, 3: +4.1 %%, profiles/README.md). The per-launch roofline pass always runs on ONE stream.")
     ap.add_argument("--points", type=int, default=160000)
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else the bench measures and checks: the "
+                    "roofline and hbm_stages passes, the results_digest check against a single-stream re-run, the N = 1 extras, the CPU "
+                    "baseline (--mode train: the conv profile, the timed all-reduce and the cross-rank checks). Each of them can still be "
+                    "switched off with its --no-* option. Off by default: a plain run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned as DIR/<name>.npy (float32; rank 0): infer = every frame's pred_boxes / pred_scores / pred_labels, "
+                    "concatenated in frame order, and boxes_per_frame; train = loss, hm_loss, loc_loss and a fixed sample of the "
+                    "updated parameters; over 64 MB in all, a fixed, seeded sample of the rows. Inputs are seeded: the same arguments give the "
+                    "same inputs in every run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra measurements the default N = 1 run appends to its line "
+    ap.add_argument("--no-extras", action="store_true", help="skip the extra measurements the default N = 1 --full run appends to its line "
                     "(fp32-MFMA value, batch-4 and 1-frame figures, the config-3 train step)")
-    ap.add_argument("--layers", action="store_true", help="print a per-launch table of the conv kernels (stderr)")
+    ap.add_argument("--layers", action="store_true", help="print a per-launch table of the conv kernels (stderr; made by the per-launch profile pass of a --full run)")
     ap.add_argument("--row-order", choices=["bricks", "taps", "canonical"], default="taps",
                     help="internal row order of the strided sparse levels (ModelConfig.row_order)")
     ap.add_argument("--row-order-chunk", type=int, default=4096)
@@ -135,15 +147,53 @@ def parse():
     ap.add_argument("--api", choices=["engine", "modules"], default="engine",
                     help="engine = the fused CenterPointEngine (headline); modules = the drop-in module path: device voxelizer -> "
                          "batch_dict -> cpd_amd.models.CenterPoint (eval), spconv.install(conv_math=--conv-math)")
-    ap.add_argument("--no-digest-check", action="store_true", help="do not re-run steps on one stream to compare their results_digest "
-                    "with the timed (multi-stream) steps'")
+    ap.add_argument("--no-digest-check", action="store_true", help="--full: do not re-run steps on one stream to compare their "
+                    "results_digest with the timed (multi-stream) steps'")
     ap.add_argument("--launch-check", action="store_true", help="only launch the --gpus ranks, rendezvous, run the timing "
                     "collectives (barrier, max over ranks) and print the n_gpus line: no GPU work (the CPU test of the N > 1 "
                     "launcher, backend from CPD_DIST_BACKEND)")
     args = ap.parse_args()
     if args.frames is None:
         args.frames = 48 if args.mode == "infer" else 1
+    if not args.full:                 # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_roofline = args.no_extras = True
+        if args.layers:
+            print("bench.py: --layers prints the table of the per-launch profile pass, which runs with --full only: no table in this run",
+                  file=sys.stderr)
     return args
+
+
+DUMP_BYTES = 64 * 10 ** 6            # --dump-outputs: at most this many bytes on disk in all (.npy headers included)
+NPY_HEADER = 128                      # bytes before the data of a .npy file of up to a few dimensions (numpy format 1.0)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy, float32. Over DUMP_BYTES in all, every array of more than one row keeps
+    a fixed, seeded sample of its rows, in order: arrays with the same number of rows keep the same rows (boxes and their scores stay
+    paired), and a run with the same shapes keeps the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for k, v in arrays.items()}
+    rows = {k: a.ndim > 0 and a.shape[0] > 1 for k, a in arrays.items()}            # arrays that can be cut down
+    fixed = sum(a.nbytes for k, a in arrays.items() if not rows[k]) + NPY_HEADER * len(arrays)
+    cut = sum(a.nbytes for k, a in arrays.items() if rows[k])
+    if fixed > DUMP_BYTES:
+        raise SystemExit("bench.py: --dump-outputs: the single-row outputs alone exceed %d bytes" % DUMP_BYTES)
+    scale = min(1.0, (DUMP_BYTES - fixed) / cut) if cut else 1.0
+    for name, a in sorted(arrays.items()):
+        if rows[name] and scale < 1.0:
+            keep = int(a.shape[0] * scale)                  # floor: the kept rows of all arrays fit the budget together
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def detection_arrays(results):
+    """one step's per-frame detections -> {key: all frames' rows concatenated in frame order, boxes_per_frame}"""
+    def host(t):
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+    keys = sorted(results[0].keys()) if results else ["pred_boxes", "pred_labels", "pred_scores"]
+    out = {k: np.concatenate([host(r[k]) for r in results]) if results else np.zeros((0,), np.float32) for k in keys}
+    out["boxes_per_frame"] = np.array([host(r["pred_boxes"]).shape[0] for r in results])
+    return out
 
 
 class ConvProfiler:
@@ -866,14 +916,21 @@ def train_main(args, cfg, sd, dev, rank, world, distributed):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, _ = step(args.warmup + i)
+        loss, parts = step(args.warmup + i)
     torch.cuda.synchronize()
     dist_utils.barrier()
     local_elapsed = time.perf_counter() - t0
     elapsed = dist_utils.max_over_ranks(local_elapsed, device="cuda" if distributed else "cpu")
     per_rank = dist_utils.gather_floats(local_elapsed, device="cuda" if distributed else "cpu")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (its loss terms) and what it updated (a fixed sample of the flat parameter buffer)
+        flat = tr.store.flat
+        sample = torch.from_numpy(np.sort(np.random.default_rng(0).choice(flat.numel(), min(flat.numel(), 1 << 20), replace=False)))
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1).cpu(), "hm_loss": parts["hm_loss"].reshape(1).cpu(),
+                                         "loc_loss": parts["loc_loss"].reshape(1).cpu(),
+                                         "params_sample": flat.detach().reshape(-1)[sample.to(flat.device)].cpu()})
     comm = None
-    if distributed:
+    if distributed and args.full:
         # the step's one collective, timed: (a) in place, HIP events around it in three more steps (includes waiting for the slowest
         # rank's backward); (b) alone, ten back-to-back all-reduces of the same flat buffer (ring / direct bandwidth over xGMI)
         tr.allreduce_events = []
@@ -914,11 +971,12 @@ def train_main(args, cfg, sd, dev, rank, world, distributed):
     }
     if world > 1:
         dd = "cuda" if distributed else "cpu"
+        out["per_rank"] = {"elapsed_s": per_rank, "frames_per_s": [args.steps * B / t for t in per_rank]}
+    if world > 1 and args.full:
         # data-parallel invariants, checked across ranks: disjoint frame shards, identical parameters after the last step
-        out["per_rank"] = {"elapsed_s": per_rank, "frames_per_s": [args.steps * B / t for t in per_rank],
-                           "first_frame_seed": [int(v) for v in dist_utils.gather_floats(seeds[0], device=dd)],
-                           "param_checksum": dist_utils.gather_floats(float(tr.store.flat.double().abs().sum()), device=dd),
-                           "param_first_words": dist_utils.gather_floats(float(tr.store.flat[:4096].double().sum()), device=dd)}
+        out["per_rank"].update({"first_frame_seed": [int(v) for v in dist_utils.gather_floats(seeds[0], device=dd)],
+                                "param_checksum": dist_utils.gather_floats(float(tr.store.flat.double().abs().sum()), device=dd),
+                                "param_first_words": dist_utils.gather_floats(float(tr.store.flat[:4096].double().sum()), device=dd)})
         pc = out["per_rank"]["param_checksum"]
         out["per_rank"]["parameters_identical_across_ranks"] = all(v == pc[0] for v in pc)
         out["collective"] = comm
@@ -1080,8 +1138,10 @@ def main():
     # label of every frame (cpd_amd/digest.py). Step i of any run of this configuration sees the same frames, so the single-stream
     # pass below must reproduce these digests bit for bit -- the check that two batches in flight on two HIP streams computed what
     # one stream computes.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, detection_arrays(timed_results[max(timed_results)]))
     from cpd_amd.digest import step_digest
-    timed_digests = {i: step_digest(r) for i, r in sorted(timed_results.items())}
+    timed_digests = {i: step_digest(r) for i, r in sorted(timed_results.items())} if args.full else {}
     timed_results.clear()
 
     out = {
@@ -1211,27 +1271,28 @@ def main():
         out["hbm_stages"]["note"] = ("algorithmic bytes (SURVEY 8d) / HIP-event time of each call (one call = all its launches), "
                                      "single stream; peak = 8 TB/s nominal HBM3E")
 
-    # results_digest: the timed steps (S batches in flight) against the same steps on ONE stream
-    if not single_results and not args.no_digest_check:
-        run_steps(min(2, args.steps), 1, keep=single_results)
-        torch.cuda.synchronize()
-    single_digests = {i: step_digest(r) for i, r in sorted(single_results.items())}
-    single_results.clear()
-    common = sorted(set(single_digests) & set(timed_digests))
-    mismatch = [i for i in common if single_digests[i] != timed_digests[i]]
-    d0 = timed_digests[min(timed_digests)] if timed_digests else ([], [], None)
-    out["results_digest"] = {
-        "timed_steps": [timed_digests[i][2] for i in sorted(timed_digests)],
-        "boxes_per_frame_step0": d0[0], "boxes_step0": sum(d0[0]),
-        "single_stream_steps": [single_digests[i][2] for i in sorted(single_digests)],
-        "steps_compared": len(common), "equal_to_single_stream_pass": (not mismatch) if common else None,
-        "all_timed_steps_equal": (len({timed_digests[i][2] for i in timed_digests}) == 1) if (timed_digests and POOL % B == 0 and B == POOL) else None,
-        "note": "per step: BLAKE2 over every frame's kept boxes / scores / labels (cpd_amd/digest.py). The timed region ran %d batch(es) "
-                "in flight on %d HIP stream(s) / worker thread(s); the single-stream pass re-ran the same steps on one stream after "
-                "the clock stopped. Equal digests = bit-identical detections." % (S, S)}
-    if mismatch and not args.no_digest_check:
-        print(json.dumps(out["results_digest"]), file=sys.stderr)
-        raise SystemExit("bench.py: results of timed step(s) %s differ from the single-stream pass (results_digest)" % mismatch)
+    if args.full:
+        # results_digest: the timed steps (S batches in flight) against the same steps on ONE stream
+        if not single_results and not args.no_digest_check:
+            run_steps(min(2, args.steps), 1, keep=single_results)
+            torch.cuda.synchronize()
+        single_digests = {i: step_digest(r) for i, r in sorted(single_results.items())}
+        single_results.clear()
+        common = sorted(set(single_digests) & set(timed_digests))
+        mismatch = [i for i in common if single_digests[i] != timed_digests[i]]
+        d0 = timed_digests[min(timed_digests)] if timed_digests else ([], [], None)
+        out["results_digest"] = {
+            "timed_steps": [timed_digests[i][2] for i in sorted(timed_digests)],
+            "boxes_per_frame_step0": d0[0], "boxes_step0": sum(d0[0]),
+            "single_stream_steps": [single_digests[i][2] for i in sorted(single_digests)],
+            "steps_compared": len(common), "equal_to_single_stream_pass": (not mismatch) if common else None,
+            "all_timed_steps_equal": (len({timed_digests[i][2] for i in timed_digests}) == 1) if (timed_digests and POOL % B == 0 and B == POOL) else None,
+            "note": "per step: BLAKE2 over every frame's kept boxes / scores / labels (cpd_amd/digest.py). The timed region ran %d batch(es) "
+                    "in flight on %d HIP stream(s) / worker thread(s); the single-stream pass re-ran the same steps on one stream after "
+                    "the clock stopped. Equal digests = bit-identical detections." % (S, S)}
+        if mismatch and not args.no_digest_check:
+            print(json.dumps(out["results_digest"]), file=sys.stderr)
+            raise SystemExit("bench.py: results of timed step(s) %s differ from the single-stream pass (results_digest)" % mismatch)
     if world > 1:
         out["per_rank"] = {"elapsed_s": per_rank, "frames_per_s": [args.steps * B / t for t in per_rank],
                            "note": "each rank's own clock around its %d timed steps (value uses the slowest)" % args.steps}

@@ -1192,5 +1192,31 @@ def main():
             print("  %-22s %8d B" % (f, os.path.getsize(os.path.join(HERE, f))))
 
 
+def compiled_reference_fixture():
+    """compiled_reference.npz: the compiled reference (oracle/_ref: iou3d_cpu.cpp boxes_iou_bev_cpu, roiaware_pool3d.cpp
+    points_in_boxes_cpu) on exactly the inputs of the tests that compare the oracle with it -- the inputs come from those tests'
+    own helpers, so the recording and the tests cannot drift apart. The tests read the recording anywhere and re-check it
+    against the live reference where oracle/_ref is built. Usage:  python tests/golden/make_golden.py compiled_reference"""
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from oracle.binding import load_reference_iou, load_reference_points_in_boxes
+    import test_oracle_golden
+    import test_prefilter
+    iou, pib = load_reference_iou(), load_reference_points_in_boxes()
+    if iou is None or pib is None:
+        raise SystemExit("build oracle/_ref first: make -C oracle ref")
+    out = {}
+    for prefix, (boxes, pts) in (("pib", test_prefilter._random_case()), ("pib_faces", test_prefilter._face_case())):
+        out[prefix + ".boxes"], out[prefix + ".points"] = boxes, pts
+        out[prefix + ".mask"] = np.asarray(pib(boxes, pts)).astype(np.uint8)        # 0/1: stored as bytes
+    b = test_oracle_golden._live_iou_boxes()
+    out["iou.boxes"], out["iou.iou"] = b, iou(b, b)
+    np.savez_compressed(os.path.join(HERE, "compiled_reference.npz"), **out)
+    print("compiled_reference: %s" % ", ".join("%s %s" % (k, v.shape) for k, v in out.items()))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["compiled_reference"]:
+        compiled_reference_fixture()
+    else:
+        main()

@@ -37,7 +37,7 @@ def _bench(*argv, timeout=1500):
 
 def test_two_rank_inference_bench_over_rccl(hip):
     _need_two_gpus()
-    d = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "8", "--no-extras", "--no-cpu-baseline", "--no-roofline")
+    d = _bench("--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "8", "--no-extras", "--no-cpu-baseline", "--no-roofline")
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert len(d["per_rank"]["elapsed_s"]) == 2 and all(t > 0 for t in d["per_rank"]["elapsed_s"])
     assert abs(d["value"] - 2 * 3 * 8 / max(d["per_rank"]["elapsed_s"])) <= 0.05 * d["value"]     # whole job over the slowest rank
@@ -46,7 +46,7 @@ def test_two_rank_inference_bench_over_rccl(hip):
 
 def test_two_rank_train_step_over_rccl(hip):
     _need_two_gpus()
-    d = _bench("--mode", "train", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-roofline")
+    d = _bench("--full", "--mode", "train", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-roofline")
     assert d["n_gpus"] == 2
     pr = d["per_rank"]
     assert pr["first_frame_seed"][0] != pr["first_frame_seed"][1]                  # disjoint frame shards
@@ -63,7 +63,7 @@ def test_two_rank_train_bench_on_one_gpu_over_gloo(hip):
     env_backup = os.environ.get("CPD_DIST_BACKEND")
     os.environ["CPD_DIST_BACKEND"] = "gloo"
     try:
-        d = _bench("--mode", "train", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-roofline")
+        d = _bench("--full", "--mode", "train", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-roofline")
     finally:
         if env_backup is None:
             os.environ.pop("CPD_DIST_BACKEND", None)

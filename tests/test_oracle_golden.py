@@ -1,5 +1,6 @@
 """Pin the CPU oracle against golden vectors produced by the reference itself
-(tests/golden/make_golden.py) and, when built, against the compiled reference iou3d_cpu.cpp."""
+(tests/golden/make_golden.py) and against the compiled reference iou3d_cpu.cpp (its recorded output; live as well where
+oracle/_ref is built)."""
 import numpy as np
 import pytest
 
@@ -94,16 +95,27 @@ def test_iou_bev_matches_reference_golden(oracle, golden):
     np.testing.assert_array_equal(np.nan_to_num(got, nan=-1), np.nan_to_num(g["iou_adv"], nan=-1))
 
 
-def test_iou_bev_matches_compiled_reference_live(oracle):
-    from oracle import load_reference_iou
-    ref = load_reference_iou()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+def _live_iou_boxes():
+    """the boxes of the live comparison (tests/golden/compiled_reference.npz, `iou.*`)"""
     rng = np.random.default_rng(7)
     n = 256
     b = np.zeros((n, 7), np.float32)
     b[:, :2] = rng.uniform(-8, 8, (n, 2)); b[:, 3:6] = rng.uniform(0.5, 5, (n, 3)); b[:, 6] = rng.uniform(-4, 4, n)
-    np.testing.assert_array_equal(oracle.boxes_iou_bev(b, b), ref(b, b))
+    return b
+
+
+def test_iou_bev_matches_compiled_reference_live(oracle, golden):
+    """against the compiled reference's recorded output for these boxes (runs anywhere); where oracle/_ref is built, the live
+    reference must reproduce the recording"""
+    b = _live_iou_boxes()
+    g = golden("compiled_reference")
+    np.testing.assert_array_equal(b, g["iou.boxes"])
+    want = g["iou.iou"]
+    from oracle import load_reference_iou
+    ref = load_reference_iou()
+    if ref is not None:
+        np.testing.assert_array_equal(ref(b, b), want)
+    np.testing.assert_array_equal(oracle.boxes_iou_bev(b, b), want)
 
 
 @pytest.mark.parametrize("tag", ["n64", "n500", "n500_t3", "n1000_t1"])

@@ -31,14 +31,43 @@ def _not_borderline(boxes, pts, margin, tol=1e-4):
     return ok
 
 
-def test_oracle_points_in_boxes_matches_compiled_reference(oracle):
+def _random_case():
+    """the boxes x points of the first compiled-reference comparison (tests/golden/compiled_reference.npz, `pib.*`)"""
+    return _boxes_pts(np.random.default_rng(3), 40, 4000)
+
+
+def _face_case():
+    """boxes x points with points placed on / next to faces and on the 1e-2 margin shell (compiled_reference.npz, `pib_faces.*`)"""
+    rng = np.random.default_rng(3)
+    k, n = 25, 6000
+    boxes = np.concatenate([rng.uniform(-20, 20, (k, 2)), rng.uniform(-1, 1, (k, 1)), rng.uniform(0.5, 6, (k, 3)), rng.uniform(-3.2, 3.2, (k, 1))], 1).astype(np.float32)
+    pts = np.concatenate([rng.uniform(-24, 24, (n, 2)), rng.uniform(-3, 3, (n, 1))], 1).astype(np.float32)
+    for i in range(k):
+        b = boxes[i]
+        c, s = np.cos(b[6]), np.sin(b[6])
+        for j, (fx, fy, fz) in enumerate([(0.5, 0, 0), (0.5 + 0.01 / b[3], 0, 0), (0, 0.5 + 0.0099 / b[4], 0), (0, 0, 0.5), (0, 0, 0.50001)]):
+            lx, ly, lz = fx * b[3], fy * b[4], fz * b[5]
+            pts[i * 5 + j] = [lx * c - ly * s + b[0], lx * s + ly * c + b[1], lz + b[2]]
+    return boxes, pts
+
+
+def _compiled_reference_mask(golden, prefix, boxes, pts):
+    """the compiled reference's points_in_boxes_cpu mask of this case: recorded in tests/golden/compiled_reference.npz (runs
+    anywhere); where oracle/_ref is built, the live reference must reproduce the recording"""
+    g = golden("compiled_reference")
+    np.testing.assert_array_equal(boxes, g[prefix + ".boxes"])
+    np.testing.assert_array_equal(pts, g[prefix + ".points"])
+    mask = g[prefix + ".mask"].astype(np.int32)
     from oracle.binding import load_reference_points_in_boxes
     ref = load_reference_points_in_boxes()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (make -C oracle ref; build container only)")
-    rng = np.random.default_rng(3)
-    boxes, pts = _boxes_pts(rng, 40, 4000)
-    mask = ref(boxes, pts)                                     # (N, M) 0/1, MARGIN 1e-2 (roiaware_pool3d.cpp:131)
+    if ref is not None:
+        np.testing.assert_array_equal(ref(boxes, pts), mask)
+    return mask
+
+
+def test_oracle_points_in_boxes_matches_compiled_reference(oracle, golden):
+    boxes, pts = _random_case()
+    mask = _compiled_reference_mask(golden, "pib", boxes, pts)  # (N, M) 0/1, MARGIN 1e-2 (roiaware_pool3d.cpp:131)
     first = np.where(mask.any(0), mask.argmax(0), -1).astype(np.int32)
     got = oracle.points_in_boxes(boxes[None], pts[None], margin=1e-2)[0]
     ok = _not_borderline(boxes, pts, 1e-2)
@@ -173,19 +202,6 @@ def test_oracle_points_in_boxes_mask_matches_reference_fixture(oracle, golden):
     np.testing.assert_array_equal(oracle.points_in_boxes_mask(g["boxes"], g["points"]), g["mask"])
 
 
-def test_oracle_points_in_boxes_mask_matches_compiled_reference(oracle):
-    from oracle.binding import load_reference_points_in_boxes
-    ref = load_reference_points_in_boxes()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(3)
-    k, n = 25, 6000
-    boxes = np.concatenate([rng.uniform(-20, 20, (k, 2)), rng.uniform(-1, 1, (k, 1)), rng.uniform(0.5, 6, (k, 3)), rng.uniform(-3.2, 3.2, (k, 1))], 1).astype(np.float32)
-    pts = np.concatenate([rng.uniform(-24, 24, (n, 2)), rng.uniform(-3, 3, (n, 1))], 1).astype(np.float32)
-    for i in range(k):
-        b = boxes[i]
-        c, s = np.cos(b[6]), np.sin(b[6])
-        for j, (fx, fy, fz) in enumerate([(0.5, 0, 0), (0.5 + 0.01 / b[3], 0, 0), (0, 0.5 + 0.0099 / b[4], 0), (0, 0, 0.5), (0, 0, 0.50001)]):
-            lx, ly, lz = fx * b[3], fy * b[4], fz * b[5]
-            pts[i * 5 + j] = [lx * c - ly * s + b[0], lx * s + ly * c + b[1], lz + b[2]]
-    np.testing.assert_array_equal(oracle.points_in_boxes_mask(boxes, pts), ref(boxes, pts))
+def test_oracle_points_in_boxes_mask_matches_compiled_reference(oracle, golden):
+    boxes, pts = _face_case()
+    np.testing.assert_array_equal(oracle.points_in_boxes_mask(boxes, pts), _compiled_reference_mask(golden, "pib_faces", boxes, pts))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of two bench.py configurations, kernel by kernel: tools/ab_kernels.py "<args A>" "<args B>" [rounds]
-Runs bench.py --no-extras --no-cpu-baseline with each argument string alternately and prints value + per-kernel ms/frame."""
+Runs bench.py --full --no-extras --no-cpu-baseline with each argument string alternately and prints value + per-kernel ms/frame."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 res = {a: [], b: []}
 for r in range(rounds):
     for cfg in (a, b):
-        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-extras", "--no-cpu-baseline"] + cfg.split(),
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline"] + cfg.split(),
                              capture_output=True, text=True)
         try:
             res[cfg].append(json.loads(out.stdout.strip().splitlines()[-1]))

@@ -4,7 +4,7 @@ rounds=$1; shift
 for r in $(seq $rounds); do
   for lib in "$@"; do
     if [ "$lib" = "-" ]; then unset CPD_HIP_LIB; else export CPD_HIP_LIB=$PWD/$lib; fi
-    python bench.py --no-extras --no-cpu-baseline --streams 1 --no-digest-check > /tmp/ab_lib.json 2>/dev/null
+    python bench.py --full --no-extras --no-cpu-baseline --streams 1 --no-digest-check > /tmp/ab_lib.json 2>/dev/null
     python - "$lib" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_lib.json"))

@@ -5,7 +5,8 @@ rounds=$1; A=$2; B=$3; shift 4
 export CPD_HIP_LIB=$PWD/cpd_amd/csrc/libcpd_hip.so
 for r in $(seq $rounds); do
   for d in "$A" "$B"; do
-    (cd $d && python bench.py --no-extras --no-cpu-baseline --no-roofline --no-digest-check "$@" 2>/dev/null) | python -c "
+    full=$(grep -q -- '"--full"' $d/bench.py && echo --full)     # (a tree from before the option prints its digest without it)
+    (cd $d && python bench.py $full --no-extras --no-cpu-baseline --no-roofline --no-digest-check "$@" 2>/dev/null) | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('%-12s %8.1f frames/s  %.3f ms/step  digest %s' % (sys.argv[1], d['value'], d['ms_per_step'], (d.get('results_digest') or {}).get('timed_steps',['-'])[0]))" "$d"
   done
 done

@@ -1,15 +1,16 @@
 #!/bin/bash
 # Train-step bench + rocprofv3 kernel stats (run on the GPU box through gpurun).
-mkdir -p gpurun_out
-python bench.py --mode train --steps 8 --warmup 4 > gpurun_out/train_bench.json 2> gpurun_out/train_bench.err
-cat gpurun_out/train_bench.json
+OUT=${OUT:-$PWD/bench_out}
+mkdir -p $OUT
+python bench.py --full --mode train --steps 8 --warmup 4 > $OUT/train_bench.json 2> $OUT/train_bench.err
+cat $OUT/train_bench.json
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
-rm -rf $R/gpurun_out/train_prof
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/train_prof -- python $R/bench.py --mode train --steps 8 --warmup 4 --no-roofline > $R/gpurun_out/train_bench_under_rocprof.json 2>/dev/null
+rm -rf $OUT/train_prof
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train_prof -- python $R/bench.py --mode train --steps 8 --warmup 4 --no-roofline > $OUT/train_bench_under_rocprof.json 2>/dev/null
 cd $R
-f=$(ls gpurun_out/train_prof/*/*kernel_stats.csv | head -1)
-cp $f gpurun_out/train_kernel_stats.csv
+f=$(ls $OUT/train_prof/*/*kernel_stats.csv | head -1)
+cp $f $OUT/train_kernel_stats.csv
 python - "$f" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
