@@ -341,6 +341,26 @@ class AnchorHeadSingle(torch.nn.Module):
                                 lw["cls_weight"], lw["loc_weight"], lw.get("dir_weight", 0.2), lw["code_weights"],
                                 self.model_cfg.get("DIR_OFFSET", 0.78539), self.num_dir_bins)
 
+    def get_training_loss(self):
+        """AnchorHeadTemplate.get_loss in the reference's contract (anchor_head_template.py:321-334): (rpn_loss, tb_dict) with rpn_loss
+        a 0-dim tensor that backward() reaches the predictions through -- the fused kernel of get_loss() behind an autograd function
+        (its gradient is the kernel's) -- and tb_dict = rpn_loss_cls, rpn_loss_loc, rpn_loss_dir (with a direction classifier),
+        rpn_loss, read back in one copy."""
+        from .autograd_ops import FusedLoss
+        f = self.forward_ret_dict
+        dirs = f.get("dir_cls_preds")
+
+        def fused():
+            losses, grads = self.get_loss()
+            return (losses, *grads)
+        total, losses = FusedLoss.apply(fused, f["cls_preds"], f["box_preds"], dirs)
+        lv = losses.tolist()
+        tb = {"rpn_loss_cls": lv[1], "rpn_loss_loc": lv[2]}
+        if dirs is not None:
+            tb["rpn_loss_dir"] = lv[3]
+        tb["rpn_loss"] = lv[0]
+        return total, tb
+
     def _predict(self, data_dict, cls_preds, box_preds, dir_preds):
         """generate_predicted_boxes on detached predictions (eval, or training with predict_boxes_when_training: l.183-190)."""
         with torch.no_grad():

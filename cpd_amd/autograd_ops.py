@@ -267,3 +267,23 @@ class HipPointwiseConv2d(torch.nn.Conv2d):
         spec = ConvSpec(None, 1, rows.shape[0], dense=True, math=self.conv_math, mode="same", packed=self._packed())
         y = gather_conv(rows, self.weight[:, :, 0, 0].t().unsqueeze(0), self.bias, spec)
         return y.view(b, h, w, self.out_channels).permute(0, 3, 1, 2)
+
+
+class FusedLoss(torch.autograd.Function):
+    """A loss computed together with its gradient by one kernel: forward returns (total as a 0-dim tensor, the kernel's loss vector,
+    non-differentiable); backward hands the saved gradients on, scaled by the incoming one. `fn()` -> (losses, grads...) with one
+    gradient per tensor of `inputs`, shaped like it (None for an input given as None). Used by the fused loss kernels
+    (cpd_anchor_loss, cpd_rcnn_loss)."""
+
+    @staticmethod
+    def forward(ctx, fn, *inputs):
+        losses, *grads = fn()
+        ctx.save_for_backward(*[g if g is not None else torch.empty(0) for g in grads])
+        ctx.present = [g is not None for g in grads]
+        ctx.mark_non_differentiable(losses)
+        return losses[0].clone(), losses
+
+    @staticmethod
+    def backward(ctx, grad_total, _grad_losses):
+        out = [g * grad_total if present else None for g, present in zip(ctx.saved_tensors, ctx.present)]
+        return (None, *out)

@@ -1128,7 +1128,10 @@ class VoxelRCNN(CenterPoint):
     def forward(self, batch_dict):
         batch_dict = self._run_modules(batch_dict)          # (fast eval: the first stage inside the optimistic range pass, CenterPoint._run_modules;
         if self.training:                                   # the RoI head reads the pooled levels' `.features` -- fp32 rows, decoded on demand)
-            loss_rpn, tb_dict = self.dense_head.get_loss()
+            # anchor dense heads (dbscan / oyster): get_loss() is the fused kernel's (losses, gradients); get_training_loss() is the
+            # reference's (loss, tb_dict) contract over it
+            dense_loss = self.dense_head.get_loss if self.model_cfg.DENSE_HEAD.NAME == "CenterHead" else self.dense_head.get_training_loss
+            loss_rpn, tb_dict = dense_loss()
             loss_rcnn, tb_dict = self.roi_head.get_loss(tb_dict)
             return {"loss": loss_rpn + loss_rcnn}, tb_dict, {}
         pred_dicts, recall = self.post_processing(batch_dict)

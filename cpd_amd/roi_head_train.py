@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .autograd_ops import HipBatchNorm1d, HipConv1d, HipLinear
+from .autograd_ops import FusedLoss, HipBatchNorm1d, HipConv1d, HipLinear
 from . import roi_pool as rp
 
 TWO_PI = 2 * np.pi
@@ -106,6 +106,93 @@ def bb_loss(pred, target):
     angle_factor = 1.25 * (1.0 - torch.abs(torch.cos(pred[:, -1] - target[:, -1])))
     dist2 = torch.pow(target[:, 0:3] - pred[:, 0:3], 2).sum(-1)
     return (1 - iou + angle_factor + dist2) * 1.5
+
+
+def rcnn_head_loss_torch(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, code_weights,
+                         cls_weight=1.0, reg_weight=1.0, corner_weight=1.0, corner_regularization=True):
+    """RoIHeadTemplate.get_loss (roi_head_template.py:148-267: get_box_cls_layer_loss + get_box_reg_layer_loss, BinaryCrossEntropy and
+    smooth-l1) in torch on the helpers above -- the restatement `cpd_rcnn_loss` is tested against, itself pinned on the reference's
+    output (tests/golden/rcnn_loss.npz). Rows: rcnn_cls [N(, 1)], rcnn_reg [N, 7], rois / gt_of_rois / gt_of_rois_src [..., >= 7]
+    (flattened to N rows), reg_valid_mask / rcnn_cls_labels [N]. Differentiable in rcnn_cls / rcnn_reg.
+    -> (total, {"rcnn_loss_cls", "rcnn_loss_reg" (the smooth-L1 part), "rcnn_loss_corner" (only with the regularisation and fg > 0),
+    "rcnn_loss_bb", "fg"}) as tensors (fg: an int)."""
+    labels = rcnn_cls_labels.reshape(-1).float()
+    n = labels.shape[0]
+    valid = (labels >= 0).float()
+    # (the ignored rows go in as 0: torch rejects targets outside [0, 1]; their terms are masked out, as in the reference)
+    bce = F.binary_cross_entropy(torch.sigmoid(rcnn_cls.reshape(-1)), torch.where(labels >= 0, labels, torch.zeros_like(labels)), reduction="none")
+    cls = (bce * valid).sum() / torch.clamp(valid.sum(), min=1.0) * cls_weight
+    gt_ct = gt_of_rois.reshape(n, -1)[:, 0:7].clone()
+    # encode_torch clamps the gt's sizes IN PLACE (box_coder_utils.py:23, on a view of forward_ret_dict['gt_of_rois']): the bb term
+    # further down reads them clamped
+    gt_ct[:, 3:6] = gt_ct[:, 3:6].clamp_min(1e-5)
+    gt_src = gt_of_rois_src.reshape(n, -1)[:, 0:7]
+    reg = rcnn_reg.reshape(n, -1)
+    roi = rois.reshape(n, -1)[:, 0:7].detach()
+    fg = reg_valid_mask.reshape(-1) > 0
+    fg_sum = int(fg.long().sum())
+    anchor = roi.clone()
+    anchor[:, 0:3] = 0
+    anchor[:, 6] = 0
+    target = residual_encode(gt_ct, anchor)
+    target = torch.where(torch.isnan(target), reg, target)
+    cw = torch.as_tensor(code_weights, dtype=torch.float32, device=reg.device).view(1, -1)
+    sl1 = smooth_l1((reg - target) * cw, 1.0 / 9.0)
+    reg_loss = (sl1 * fg.unsqueeze(-1).float()).sum() / max(fg_sum, 1) * reg_weight
+    terms = {"rcnn_loss_cls": cls, "rcnn_loss_reg": reg_loss}
+    total = cls + reg_loss
+    if corner_regularization and fg_sum > 0:
+        fg_roi = roi[fg]
+        anchors = fg_roi.clone()
+        anchors[:, 0:3] = 0
+        boxes = residual_decode(reg[fg], anchors)
+        boxes = rotate_points_along_z(boxes.unsqueeze(1), fg_roi[:, 6]).squeeze(1)
+        boxes = torch.cat([boxes[:, 0:3] + fg_roi[:, 0:3], boxes[:, 3:]], dim=-1)
+        corner = corner_loss_lidar(boxes[:, 0:7], gt_src[fg]).mean() * corner_weight
+        terms["rcnn_loss_corner"] = corner
+        total = total + corner
+    local = roi.clone()
+    local[:, 0:3] = 0
+    local[:, 6] = 0
+    pred = residual_decode(reg, local)
+    bb = bb_loss(pred[fg], gt_ct[fg]).sum() / (fg_sum + 1) if fg_sum > 0 else reg.new_zeros(())
+    terms["rcnn_loss_bb"] = bb
+    terms["fg"] = fg_sum
+    return total + bb, terms
+
+
+def rcnn_loss_fused(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, code_weights,
+                    cls_weight=1.0, reg_weight=1.0, corner_weight=1.0, corner_regularization=True):
+    """`cpd_rcnn_loss`: the loss of rcnn_head_loss_torch and its gradient in one launch, nothing read back.
+    -> (losses [6] = total, cls, reg, corner, bb, fg on the device, d_cls shaped like rcnn_cls, d_reg shaped like rcnn_reg)."""
+    from ._lib import check, farr, lib, ptr, stream
+    n = rcnn_reg.numel() // 7
+    dev = rcnn_reg.device
+
+    def rows(t, flat=False):
+        t = t.detach().reshape(n) if flat else t.detach().reshape(n, t.shape[-1])
+        return t.float().contiguous()
+    cls, reg = rows(rcnn_cls, True), rows(rcnn_reg)
+    roi = rows(rois)[:, 0:7].contiguous()
+    gt, src = rows(gt_of_rois), rows(gt_of_rois_src)
+    mask, labels = rows(reg_valid_mask, True), rows(rcnn_cls_labels, True)
+    assert reg.shape[1] == 7 and gt.shape[1] >= 7 and src.shape[1] >= 7, (reg.shape, gt.shape, src.shape)
+    d_cls, d_reg = torch.empty_like(cls), torch.empty_like(reg)
+    losses = torch.empty(6, dtype=torch.float32, device=dev)
+    check(lib().cpd_rcnn_loss(ptr(cls), ptr(reg), ptr(roi), ptr(gt), gt.shape[1], ptr(src), src.shape[1], ptr(mask), ptr(labels), n,
+                              farr([float(v) for v in code_weights]), float(cls_weight), float(reg_weight), float(corner_weight),
+                              int(bool(corner_regularization)), ptr(d_cls), ptr(d_reg), ptr(losses), stream()), "cpd_rcnn_loss")
+    return losses, d_cls.view(rcnn_cls.shape), d_reg.view(rcnn_reg.shape)
+
+
+def rcnn_head_loss(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, code_weights,
+                   cls_weight=1.0, reg_weight=1.0, corner_weight=1.0, corner_regularization=True):
+    """rcnn_head_loss_torch through `cpd_rcnn_loss`, differentiable in rcnn_cls / rcnn_reg (the gradient is the kernel's, saved by the
+    forward). -> (total [0-dim], losses [6] = total, cls, reg, corner, bb, fg on the device)."""
+    def fn():
+        return rcnn_loss_fused(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, code_weights,
+                               cls_weight, reg_weight, corner_weight, corner_regularization)
+    return FusedLoss.apply(fn, rcnn_cls, rcnn_reg)
 
 
 # ------------------------------------------------------------------------------------------------ proposal target layer

@@ -6,6 +6,8 @@ csrc/roi_pool.hip. Mirrors, name for name:
   grouping_operation                           cpd/ops/pointnet2/pointnet2_stack/pointnet2_utils.py:48-84
   NeighborVoxelSAModuleMSG                     cpd/ops/pointnet2/pointnet2_stack/voxel_pool_modules.py:8-131
   get_global_grid_points_of_roi, roi_grid_pool cpd/models/roi_heads/voxel_rcnn_head.py:186-273, 365-386
+  VoxelRCNNHead                                cpd/models/roi_heads/voxel_rcnn_head.py:664-913 (eval and training forward,
+                                               RoIHeadTemplate.get_loss through the fused `cpd_rcnn_loss`)
 
 In eval mode (BatchNorm folded) the per-voxel MLP (mlps_in) and the output MLP
 (mlps_out) are 1x1 `cpd_gather_conv` GEMMs; grouping, position encoding, ReLU and max-pool are one
@@ -396,11 +398,16 @@ def proposal_layer(batch_box_preds, batch_cls_preds, nms_thresh, nms_pre_maxsize
 
 
 class VoxelRCNNHead(nn.Module):
-    """Eval forward of VoxelRCNNHead (cpd/models/roi_heads/voxel_rcnn_head.py:664-760, 876-916): RoI grid pooling,
-    shared FC / cls / reg stacks (Linear + eval BatchNorm1d + ReLU folded into `cpd_gather_conv` GEMM epilogues) and
-    RoIHeadTemplate.generate_predicted_boxes (roi_head_template.py:269-299). Same constructor arguments and
-    state_dict names as the reference module; the training branch lives in cpd_amd/roi_head_train.py (VoxelRCNNProtoHead, the
-    head the shipped config selects)."""
+    """VoxelRCNNHead (cpd/models/roi_heads/voxel_rcnn_head.py:664-763, 876-916), the RoI head of the anchor-head configs
+    (voxel_rcnn_dbscan / oyster_single_train.yaml). Same constructor arguments and state_dict names as the reference module.
+
+    Eval: RoI grid pooling, shared FC / cls / reg stacks (Linear + eval BatchNorm1d + ReLU folded into `cpd_gather_conv` GEMM
+    epilogues) and RoIHeadTemplate.generate_predicted_boxes (roi_head_template.py:269-299), under no_grad.
+    Training: proposal layer at NMS_CONFIG.TRAIN, proposal-target sampling and canonical targets (roi_head_train.assign_targets),
+    the differentiable pooling path, the FC stacks as modules (batch-statistics BatchNorm, dropout) -> forward_ret_dict;
+    get_loss() is RoIHeadTemplate.get_loss in one fused loss-and-gradient launch (`cpd_rcnn_loss`, roi_head_train.rcnn_head_loss).
+    The constructor keeps torch's default initialisation of the FC stacks; init_weights() is the reference's (its constructor calls
+    it): call it before training from scratch."""
 
     def __init__(self, input_channels, model_cfg, point_cloud_range=None, voxel_size=None, num_frames=1, num_class=1, **kwargs):
         super().__init__()
@@ -432,6 +439,32 @@ class VoxelRCNNHead(nn.Module):
         self.shared_fc_layers = stack(self.grid_size ** 3 * c_out, model_cfg["SHARED_FC"])
         self.cls_layers = stack(model_cfg["SHARED_FC"][-1], model_cfg["CLS_FC"], num_class)
         self.reg_layers = stack(model_cfg["SHARED_FC"][-1], model_cfg["REG_FC"], 7 * num_class)
+        self._fc = None
+        # the training pieces (roi_head_template.py:15-28); an eval-only config may leave TARGET_CONFIG / LOSS_CONFIG out
+        from .roi_head_train import ProposalTargetLayer
+        tc, lc = model_cfg.get("TARGET_CONFIG"), model_cfg.get("LOSS_CONFIG")
+        self.proposal_target_layer = ProposalTargetLayer(tc) if tc is not None else None
+        if lc is not None:
+            self.register_buffer("code_weights", torch.tensor(lc["LOSS_WEIGHTS"]["code_weights"], dtype=torch.float32), persistent=False)
+        self.forward_ret_dict = {}
+
+    def init_weights(self):
+        """voxel_rcnn_head.py:747-763: xavier-normal on every Linear of the cls / reg stacks (bias 0), N(0, 0.01) on their output
+        layers, then xavier-normal on the shared stack -- in that order, so that equal seeds give the reference's weights."""
+        for stack in (self.cls_layers, self.reg_layers):
+            for m in stack.modules():
+                if isinstance(m, nn.Linear):
+                    nn.init.xavier_normal_(m.weight)
+                    if m.bias is not None:
+                        nn.init.constant_(m.bias, 0)
+        for stack in (self.cls_layers, self.reg_layers):
+            nn.init.normal_(stack[-1].weight, 0, 0.01)
+            nn.init.constant_(stack[-1].bias, 0)
+        for m in self.shared_fc_layers.modules():
+            if isinstance(m, nn.Linear):
+                nn.init.xavier_normal_(m.weight)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
         self._fc = None
 
     def _pack_fc(self):
@@ -471,28 +504,72 @@ class VoxelRCNNHead(nn.Module):
             rb = blocks[i]
         return (x, rb) if return_block else x
 
-    @torch.no_grad()
-    def forward(self, batch_dict):
-        if self.training:
-            raise NotImplementedError("VoxelRCNNHead: eval forward only")
-        if self._fc is None:
-            self._pack_fc()
-        if "rois" not in batch_dict:
-            # RoIHeadTemplate.proposal_layer on the dense head's predictions (voxel_rcnn_head.py:883-885, roi_head_template.py:53-114):
-            # the anchor-head configs (voxel_rcnn_dbscan / oyster) reach the RoI head this way; CenterHead already left `rois` behind
-            nms = self.model_cfg["NMS_CONFIG"]["TEST"]
+    def _proposals(self, batch_dict, mode):
+        """RoIHeadTemplate.proposal_layer on the dense head's predictions (voxel_rcnn_head.py:883-885, roi_head_template.py:53-114):
+        the anchor-head configs (voxel_rcnn_dbscan / oyster) reach the RoI head this way; CenterHead already left `rois` behind."""
+        if "rois" in batch_dict:
+            return
+        nms = self.model_cfg["NMS_CONFIG"][mode]
+        with torch.no_grad():
             rois7, roi_scores, roi_labels, _ = proposal_layer(batch_dict["batch_box_preds"], batch_dict["batch_cls_preds"], float(nms["NMS_THRESH"]),
                                                               int(nms["NMS_PRE_MAXSIZE"]), int(nms["NMS_POST_MAXSIZE"]),
                                                               first_rows="auto", device_fallback=True)
-            batch_dict.update(rois=rois7, roi_scores=roi_scores, roi_labels=roi_labels,
-                              has_class_labels=batch_dict["batch_cls_preds"].shape[-1] > 1)
-        rois, b = batch_dict["rois"], batch_dict["batch_size"]
+        batch_dict.update(rois=rois7, roi_scores=roi_scores, roi_labels=roi_labels,
+                          has_class_labels=batch_dict["batch_cls_preds"].shape[-1] > 1)
+
+    def _pool(self, batch_dict):
         levels = {}
         for name in self.sources:
             t = batch_dict["multi_scale_3d_features"][name]
             levels[name] = t if isinstance(t, tuple) else (t.features, t.indices, list(t.spatial_shape))
-        pooled = roi_grid_pool(rois, levels, batch_dict["multi_scale_3d_strides"], dict(zip(self.sources, self.roi_grid_pool_layers)),
-                               self.grid_size, self.voxel_size, self.point_cloud_range, b)
+        return roi_grid_pool(batch_dict["rois"], levels, batch_dict["multi_scale_3d_strides"], dict(zip(self.sources, self.roi_grid_pool_layers)),
+                             self.grid_size, self.voxel_size, self.point_cloud_range, batch_dict["batch_size"])
+
+    def forward(self, batch_dict):
+        if not self.training:
+            return self._forward_eval(batch_dict)
+        # training (voxel_rcnn_head.py:876-913): the packed eval FC images go stale with the first optimizer step
+        self._fc = None
+        from .roi_head_train import assign_targets
+        self._proposals(batch_dict, "TRAIN")
+        targets = assign_targets(self.proposal_target_layer, batch_dict)
+        batch_dict["rois"], batch_dict["roi_labels"] = targets["rois"], targets["roi_labels"]
+        pooled = self._pool(batch_dict)
+        shared = self.shared_fc_layers(pooled.reshape(pooled.shape[0], -1))
+        targets.update(rcnn_cls=self.cls_layers(shared), rcnn_reg=self.reg_layers(shared))
+        self.forward_ret_dict = targets
+        return batch_dict
+
+    def get_loss(self, tb_dict=None):
+        """RoIHeadTemplate.get_loss (roi_head_template.py:148-267) -> (rcnn_loss, tb_dict): one `cpd_rcnn_loss` launch for the loss and
+        its gradient, one read-back of the loss vector for tb_dict (rcnn_loss_cls, rcnn_loss_reg = the smooth-L1 part,
+        rcnn_loss_corner when the corner term is present, rcnn_loss)."""
+        from .roi_head_train import rcnn_head_loss
+        tb_dict = {} if tb_dict is None else tb_dict
+        lc = self.model_cfg["LOSS_CONFIG"]
+        if lc["CLS_LOSS"] != "BinaryCrossEntropy":
+            raise NotImplementedError(lc["CLS_LOSS"])
+        if lc["REG_LOSS"] != "smooth-l1":
+            raise NotImplementedError(lc["REG_LOSS"])
+        lw, t = lc["LOSS_WEIGHTS"], self.forward_ret_dict
+        corner = bool(lc["CORNER_LOSS_REGULARIZATION"])
+        loss, losses = rcnn_head_loss(t["rcnn_cls"], t["rcnn_reg"], t["rois"], t["gt_of_rois"], t["gt_of_rois_src"], t["reg_valid_mask"],
+                                      t["rcnn_cls_labels"], lw["code_weights"], lw["rcnn_cls_weight"], lw["rcnn_reg_weight"],
+                                      lw["rcnn_corner_weight"], corner)
+        total, cls, reg, corner_loss, _bb, fg = losses.tolist()
+        tb_dict.update(rcnn_loss_cls=cls, rcnn_loss_reg=reg)
+        if corner and fg > 0:
+            tb_dict["rcnn_loss_corner"] = corner_loss
+        tb_dict["rcnn_loss"] = total
+        return loss, tb_dict
+
+    @torch.no_grad()
+    def _forward_eval(self, batch_dict):
+        if self._fc is None:
+            self._pack_fc()
+        self._proposals(batch_dict, "TEST")
+        rois, b = batch_dict["rois"], batch_dict["batch_size"]
+        pooled = self._pool(batch_dict)
         x = pooled.reshape(pooled.shape[0], -1).contiguous()
         shared = self._run(self._fc["shared_fc_layers"], x)
         rcnn_cls = self._run(self._fc["cls_layers"], shared)

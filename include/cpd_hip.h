@@ -599,6 +599,22 @@ int cpd_anchor_loss(const float *cls_preds, const float *box_preds, const float 
                     const float code_weights[7], float cls_weight, float loc_weight, float dir_weight,
                     float *d_cls, float *d_box, float *d_dir, float *losses, void *ws,
                     size_t ws_bytes, cpd_stream_t stream);
+/* RoIHeadTemplate.get_loss (roi_head_template.py:148-267) of the anchor-head VoxelRCNN fused with its gradient, for n RoI rows
+ * (n = batch x ROI_PER_IMAGE): rcnn_cls [n], rcnn_reg / rois [n][7], gt_of_rois (canonical frame) [n][ld_gt] and gt_of_rois_src
+ * [n][ld_src] (columns 0..6 used), reg_valid_mask [n] (> 0 = foreground) and rcnn_cls_labels [n] (fractional targets, < 0 ignore),
+ * all fp32. Terms: cls = binary cross entropy on sigmoid(rcnn_cls) (torch's -100 log clamp) over the rows with label >= 0 /
+ * max(#valid, 1) x cls_weight; reg = smooth-L1 (beta 1/9, code_weights) against the ResidualCoder targets of the canonical gt (RoI
+ * with xyz and heading zeroed as the anchor, sizes clamp_min 1e-5), NaN targets ignored, sum over the foreground / max(fg, 1) x
+ * reg_weight; corner (corner_regularization and fg > 0) = get_corner_loss_lidar of the decoded boxes (RoI heading kept, rotated and
+ * moved to the RoI) against gt_of_rois_src, mean over the foreground x corner_weight; bb = bbloss.bb_loss of the boxes decoded
+ * against the RoI with xyz and heading zeroed vs the canonical gt, sum over the foreground / (fg + 1), unweighted, 0 when fg = 0.
+ * Writes d(total)/d(rcnn_cls) to d_cls [n], d(total)/d(rcnn_reg) to d_reg [n][7] and losses[6] = {total, cls, reg, corner, bb, fg}
+ * on the device. One launch, no workspace, nothing read back; deterministic (fixed-order sums, no atomics). n = 0 writes zero
+ * losses (the row pointers may then be NULL).                                                                                   */
+int cpd_rcnn_loss(const float *rcnn_cls, const float *rcnn_reg, const float *rois, const float *gt_of_rois, int ld_gt,
+                  const float *gt_of_rois_src, int ld_src, const float *reg_valid_mask, const float *rcnn_cls_labels, int n,
+                  const float code_weights[7], float cls_weight, float reg_weight, float corner_weight,
+                  int corner_regularization, float *d_cls, float *d_reg, float *losses, cpd_stream_t stream);
 /* Adam with decoupled weight decay on a flat buffer (tools/train_utils/optimization/fastai_optim.py:
  * 132-150 true_wd semantics): grad is multiplied first by grad_scale (1/world after all-reduce) and,
  * when grad_scale_dev is not NULL, by the float it points to in device memory (the clip factor of

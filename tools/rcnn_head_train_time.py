@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Times the anchor-head VoxelRCNN's RoI-head training on one GPU (numbers quoted in DESIGN.md):
+  * get_loss: the fused `cpd_rcnn_loss` (roi_head_train.rcnn_head_loss: one launch + the tb_dict read-back) against the torch
+    restatement rcnn_head_loss_torch (+ its .item() read-backs), at the shipped size B = 2, ROI_PER_IMAGE = 150, with backward;
+  * one head training step: forward (proposal layer, sampling, pooling, FC stacks) + get_loss + backward, the shipped ROI_HEAD of
+    voxel_rcnn_dbscan_single_train.yaml (GRID_SIZE 6; x_conv3 / x_conv4 with two radii each: four pooling scales) on synthetic
+    sparse levels and proposals.
+Median of cuda-event-timed repetitions after warm-up. Prints one JSON line.  Usage: python tools/rcnn_head_train_time.py"""
+import json
+import os
+import sys
+import types
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, reps=50, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+def loss_rows(n, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.rand(*s, generator=g)
+    rois = torch.cat([(r(n, 2) - 0.5) * 60, r(n, 1) - 0.5, 0.6 + 4 * r(n, 3), (r(n, 1) - 0.5) * 6.4], 1)
+    gt = torch.cat([torch.randn(n, 3, generator=g) * 0.4, rois[:, 3:6] * (0.8 + 0.4 * r(n, 3)), (r(n, 1) - 0.5) * 3, torch.ones(n, 1)], 1)
+    src = torch.cat([rois[:, 0:3] + torch.randn(n, 3, generator=g) * 0.4, gt[:, 3:6], rois[:, 6:7], torch.ones(n, 1)], 1)
+    t = dict(rcnn_cls=torch.randn(n, 1, generator=g), rcnn_reg=torch.randn(n, 7, generator=g) * 0.3, rois=rois.view(2, -1, 7),
+             gt_of_rois=gt.view(2, -1, 8), gt_of_rois_src=src.view(2, -1, 8), reg_valid_mask=(r(n) < 0.5).long().view(2, -1),
+             rcnn_cls_labels=r(n).view(2, -1))
+    return {k: v.cuda() for k, v in t.items()}
+
+
+def main():
+    from cpd_amd import models, roi_pool
+    from cpd_amd.roi_head_train import rcnn_head_loss, rcnn_head_loss_torch
+    torch.cuda.set_device(0)
+    out = {"device": torch.cuda.get_device_name(0)}
+    cfg = models.waymo_voxel_rcnn_dbscan_cfg().ROI_HEAD
+    per = int(cfg.TARGET_CONFIG["ROI_PER_IMAGE"])
+    n = 2 * per
+    t = loss_rows(n)
+    lw = cfg.LOSS_CONFIG["LOSS_WEIGHTS"]
+    w = (lw["code_weights"], lw["rcnn_cls_weight"], lw["rcnn_reg_weight"], lw["rcnn_corner_weight"], True)
+    cls, reg = t["rcnn_cls"].requires_grad_(True), t["rcnn_reg"].requires_grad_(True)
+    args = (cls, reg, t["rois"], t["gt_of_rois"], t["gt_of_rois_src"], t["reg_valid_mask"], t["rcnn_cls_labels"])
+
+    def fused():
+        loss, losses = rcnn_head_loss(*args, *w)
+        losses.tolist()                                              # the tb_dict read-back of VoxelRCNNHead.get_loss
+        loss.backward()
+
+    def restated():
+        loss, terms = rcnn_head_loss_torch(*args, *w)
+        [v.item() for k, v in terms.items() if k != "fg"]            # the reference's .item() calls
+        loss.backward()
+    out["get_loss_rows"] = n
+    out["get_loss_fused_ms"] = timed(fused)
+    out["get_loss_torch_ms"] = timed(restated)
+
+    # one head training step at the shipped ROI_HEAD
+    chans = {"x_conv1": 16, "x_conv2": 32, "x_conv3": 64, "x_conv4": 128}
+    pcr = [-75.2, -75.2, -2.0, 75.2, 75.2, 4.0]
+    vs = [0.1, 0.1, 0.15]
+    torch.manual_seed(0)
+    head = roi_pool.VoxelRCNNHead(chans, cfg, point_cloud_range=pcr, voxel_size=vs, num_class=1).cuda().train()
+    head.init_weights()
+    rng = np.random.default_rng(0)
+    B, n_gt = 2, 40
+    gt = np.zeros((B, n_gt, 8), np.float32)
+    gt[..., 0:2] = rng.uniform(-60, 60, (B, n_gt, 2))
+    gt[..., 2] = rng.uniform(-0.5, 0.5, (B, n_gt))
+    gt[..., 3:6] = [4.5, 2.0, 1.6]
+    gt[..., 6] = rng.uniform(-3, 3, (B, n_gt))
+    gt[..., 7] = 1
+    boxes = np.repeat(gt[:, :, None, :7], 100, 2)
+    boxes[..., 0:3] += rng.normal(0, 0.4, boxes[..., 0:3].shape)
+    boxes = boxes.reshape(B, -1, 7).astype(np.float32)
+    scores = rng.normal(0, 1, (B, boxes.shape[1], 3)).astype(np.float32)
+    levels = {}
+    for name, stride, nvox in (("x_conv3", 4, 60000), ("x_conv4", 8, 20000)):
+        shp = [41 // stride + 1, 1504 // stride, 1504 // stride]
+        idx = np.stack([rng.integers(0, B, nvox), rng.integers(0, shp[0], nvox), rng.integers(0, shp[1], nvox), rng.integers(0, shp[2], nvox)], 1)
+        idx = torch.from_numpy(np.unique(idx, axis=0).astype(np.int32)).cuda()
+        f = torch.randn(idx.shape[0], chans[name], device="cuda").requires_grad_(True)
+        levels[name] = types.SimpleNamespace(indices=idx, features=f, spatial_shape=shp, batch_size=B)
+    gt_t, boxes_t, scores_t = torch.from_numpy(gt).cuda(), torch.from_numpy(boxes).cuda(), torch.from_numpy(scores).cuda()
+
+    def step():
+        bd = {"batch_size": B, "batch_box_preds": boxes_t, "batch_cls_preds": scores_t, "gt_boxes": gt_t, "multi_scale_3d_features": levels,
+              "multi_scale_3d_strides": {"x_conv3": 4, "x_conv4": 8}}
+        head(bd)
+        loss, _ = head.get_loss()
+        head.zero_grad(set_to_none=True)
+        loss.backward()
+    out["head_step_rois"] = B * per
+    out["head_step_ms"] = timed(step, reps=20, warmup=3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
