@@ -131,3 +131,108 @@ def gt_boxes(seed, n=30, span=70.0):
     b[:, 6] = rng.uniform(-np.pi, np.pi, n)
     b[:, 7] = cls
     return b
+
+
+# ---- KITTI-format annotations (kitti_common label dicts) for the evaluation ----------------------------------------
+_KITTI_DIMS = {"Car": (3.9, 1.55, 1.65), "Van": (5.0, 2.1, 1.9), "Truck": (9.0, 3.2, 2.5), "Pedestrian": (0.8, 1.75, 0.6),
+               "Person_sitting": (0.8, 1.2, 0.6), "Cyclist": (1.76, 1.7, 0.6)}
+_KITTI_GT_NAMES = ["Car", "Car", "Car", "Pedestrian", "Pedestrian", "Cyclist", "Cyclist", "Van", "Person_sitting",
+                   "DontCare", "Truck"]
+
+
+def _kitti_image_box(loc, dims, rng):
+    """A plausible 2-D box for a camera-frame object (pinhole, f = 720 px, principal point (620, 190)), clipped."""
+    x, y, z = loc
+    l, h, w = dims
+    span = 720.0 * max(l, w) * 0.8 / z
+    u, v_bot, hpx = 620.0 + 720.0 * x / z, 190.0 + 720.0 * y / z, 720.0 * h / z
+    box = np.array([u - span / 2, v_bot - hpx, u + span / 2, v_bot]) + rng.normal(0, 1.0, 4)
+    return np.clip(box, [0, 0, 0, 0], [1241, 374, 1241, 374])
+
+
+def kitti_annos(n_frames, seed=0, max_gt=12, max_fp=4, p_empty_dt=0.05, p_empty_gt=0.05):
+    """Seeded (gt_annos, dt_annos) lists in kitti_common's label-dict format (float64 arrays): Car / Pedestrian / Cyclist
+    plus Van, Person_sitting, Truck and DontCare gts whose occlusion, truncation and 2-D heights span the three
+    difficulty bins; detections are jittered gts (names kept, Van sometimes detected as Car) plus false positives, with
+    two-decimal scores (ties) and valid alpha. Some frames have no gt, some no detection."""
+    rng = np.random.default_rng(seed)
+    gts, dts = [], []
+    for _ in range(n_frames):
+        n_gt = 0 if rng.random() < p_empty_gt else int(rng.integers(1, max_gt + 1))
+        g = {k: [] for k in ("name", "truncated", "occluded", "alpha", "bbox", "dimensions", "location", "rotation_y")}
+        d = {k: [] for k in ("name", "truncated", "occluded", "alpha", "bbox", "dimensions", "location", "rotation_y",
+                             "score")}
+        for _ in range(n_gt):
+            name = _KITTI_GT_NAMES[int(rng.integers(len(_KITTI_GT_NAMES)))]
+            if name == "DontCare":
+                g["name"].append(name)
+                g["truncated"].append(-1.0)
+                g["occluded"].append(-1)
+                g["alpha"].append(-10.0)
+                u, v = rng.uniform(0, 1100), rng.uniform(120, 300)
+                g["bbox"].append([u, v, u + rng.uniform(10, 140), v + rng.uniform(8, 70)])
+                g["dimensions"].append([-1.0, -1.0, -1.0])
+                g["location"].append([-1000.0, -1000.0, -1000.0])
+                g["rotation_y"].append(-10.0)
+                continue
+            dims = np.array(_KITTI_DIMS[name]) * rng.uniform(0.85, 1.15, 3)
+            loc = np.array([rng.uniform(-15, 15), rng.uniform(1.2, 2.2), rng.uniform(4, 70)])
+            ry = rng.uniform(-np.pi, np.pi)
+            bbox = _kitti_image_box(loc, dims, rng)
+            g["name"].append(name)
+            g["truncated"].append(float(rng.choice([0.0, 0.0, 0.1, 0.25, 0.4, 0.7])))
+            g["occluded"].append(int(rng.choice([0, 0, 1, 2, 3])))
+            g["alpha"].append(ry - np.arctan2(loc[0], loc[2]))
+            g["bbox"].append(bbox)
+            g["dimensions"].append(dims)
+            g["location"].append(loc)
+            g["rotation_y"].append(ry)
+            if rng.random() < 0.8:
+                scale = 0.04 * loc[2] / 10.0
+                dloc = loc + rng.normal(0, [scale, 0.05, scale])
+                ddims = dims * (1 + rng.normal(0, 0.06, 3))
+                dry = ry + rng.normal(0, 0.12) + (np.pi if rng.random() < 0.05 else 0.0)
+                dname = "Car" if name == "Van" and rng.random() < 0.5 else name
+                d["name"].append(dname)
+                d["bbox"].append(bbox + rng.normal(0, 2.0 + 30.0 / loc[2], 4))
+                d["dimensions"].append(ddims)
+                d["location"].append(dloc)
+                d["rotation_y"].append(dry)
+                d["alpha"].append(dry - np.arctan2(dloc[0], dloc[2]))
+                d["score"].append(round(float(rng.uniform(0.05, 1.0)), 2))
+        for _ in range(int(rng.integers(0, max_fp + 1))):
+            name = ["Car", "Pedestrian", "Cyclist"][int(rng.integers(3))]
+            dims = np.array(_KITTI_DIMS[name]) * rng.uniform(0.85, 1.15, 3)
+            loc = np.array([rng.uniform(-15, 15), rng.uniform(1.2, 2.2), rng.uniform(4, 70)])
+            ry = rng.uniform(-np.pi, np.pi)
+            d["name"].append(name)
+            d["bbox"].append(_kitti_image_box(loc, dims, rng))
+            d["dimensions"].append(dims)
+            d["location"].append(loc)
+            d["rotation_y"].append(ry)
+            d["alpha"].append(ry - np.arctan2(loc[0], loc[2]))
+            d["score"].append(round(float(rng.uniform(0.05, 0.9)), 2))
+        if rng.random() < p_empty_dt:
+            d = {k: [] for k in d}
+        n_dt = len(d["name"])
+        d["truncated"] = [0.0] * n_dt
+        d["occluded"] = [0] * n_dt
+        gts.append(_kitti_dict(g))
+        dts.append(_kitti_dict(d))
+    return gts, dts
+
+
+def _kitti_dict(a):
+    out = {}
+    for k, v in a.items():
+        if k == "name":
+            out[k] = np.array(v, dtype="<U14") if v else np.zeros(0, dtype="<U14")
+        elif k == "occluded":
+            out[k] = np.array(v, dtype=np.int64)
+        elif k in ("bbox",):
+            out[k] = np.array(v, dtype=np.float64).reshape(-1, 4)
+        elif k in ("dimensions", "location"):
+            out[k] = np.array(v, dtype=np.float64).reshape(-1, 3)
+        else:
+            out[k] = np.array(v, dtype=np.float64)
+    return out

@@ -776,6 +776,47 @@ int cpd_atss_assign(const float *anchors, int n_anchors, const float *gt_boxes, 
                     int match_height, float *labels, float *reg_targets, float *reg_weights, void *workspace,
                     size_t workspace_bytes, cpd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * KITTI-protocol evaluation (csrc/kitti_eval.hip): the numba / numba.cuda hot loops of
+ * cpd/datasets/kitti/kitti_object_eval_python/eval.py and rotate_iou.py, for all frames of a set at once.
+ * Frames are CSR segments: dt_off / gt_off / dc_off [n_frames + 1] int32 row offsets (device), pair_off
+ * [n_frames + 1] int64 offsets of each frame's dt x gt block in the packed overlaps (pair_off[f + 1] - pair_off[f]
+ * = n_dt(f) * n_gt(f); block row-major, dt rows, gt columns: the reference's overlaps[f]).
+ * ------------------------------------------------------------------------------------------ */
+/* calculate_iou_partly(dt_annos, gt_annos, metric) (eval.py:340-415, called at l.485) without the cross-frame blocks:
+ *   metric 0: image_box_overlap (eval.py:91-117), dt / gt [n][4] float64 bbox, `criterion` as there;
+ *   metric 1: rotate_iou_gpu_eval (rotate_iou.py:17-330), dt / gt [n][5] float32 (x, z, l, w, ry), `criterion` -1 / 0 / 1 / 2
+ *             (0 divides by the gt = query box's area: the launcher calls devRotateIoUEval(query, box), l.289-291);
+ *   metric 2: d3_box_overlap (eval.py:121-155), dt / gt [n][7] float64 camera boxes (x, y, z, l, h, w, ry): float32 BEV
+ *             intersection times the float64 height overlap over the union (`criterion` picks the divisor as in
+ *             d3_box_overlap_kernel), rounded to float32.
+ * out [n_pairs] float64. At most 8 intersection points per pair (the reference's buffer). */
+int cpd_kitti_overlaps(int metric, int criterion, const void *dt_boxes, const void *gt_boxes, const int32_t *dt_off,
+                       const int32_t *gt_off, const int64_t *pair_off, int n_frames, int64_t n_pairs, double *out,
+                       cpd_stream_t stream);
+/* Workspace of cpd_kitti_match_scores / cpd_kitti_match_pr (HOST): n_sweeps x 41 x n_frames per-frame results + flags. */
+size_t cpd_kitti_match_workspace_bytes(int n_sweeps, int n_frames, int total_dt);
+/* compute_statistics_jit(compute_fp=False) (eval.py:158-259) as eval_class's first loop calls it (l.502-517), for every
+ * sweep s (one (class, difficulty, min_overlap): ignored-flag row sweep_cd[s] of ig_gt [n_cd][total_gt] / ig_dt
+ * [n_cd][total_dt], int8 -1 / 0 / 1 from clean_data; threshold sweep_min_overlap[s]) and frame. Outputs [n_sweeps][total_gt]:
+ * matched[s][g] = 1 where the reference appends a score to `thresholds` for gt g, scores[s][g] that score (strict > on the
+ * score, lowest detection index on ties). dt_score [total_dt] float64. */
+int cpd_kitti_match_scores(const double *overlaps, const int64_t *pair_off, const int32_t *dt_off, const int32_t *gt_off,
+                           int n_frames, const int8_t *ig_gt, const int8_t *ig_dt, const double *dt_score,
+                           const int32_t *sweep_cd, const double *sweep_min_overlap, int n_sweeps, int total_gt, int total_dt,
+                           double *scores, int8_t *matched, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+/* fused_compute_statistics (eval.py:275-337) -> compute_statistics_jit(compute_fp=True) for every sweep, frame and
+ * threshold t < n_thresholds[s] of thresholds [n_sweeps][41] (get_thresholds' output), summed over frames in frame order:
+ * pr_counts [n_sweeps][41][3] int64 tp / fp / fn, pr_sim [n_sweeps][41] float64 similarity (frames whose similarity is -1
+ * skipped); rows t >= n_thresholds[s] are zero. metric 0 applies the don't-care suppression (dc_bbox [total_dc][4] float64);
+ * compute_aos adds (1 + cos(gt alpha - dt alpha)) / 2 per true positive. dt_bbox [total_dt][4], dt / gt alpha float64. */
+int cpd_kitti_match_pr(const double *overlaps, const int64_t *pair_off, const int32_t *dt_off, const int32_t *gt_off,
+                       const int32_t *dc_off, int n_frames, const int8_t *ig_gt, const int8_t *ig_dt, const double *dt_score,
+                       const double *dt_alpha, const double *gt_alpha, const double *dt_bbox, const double *dc_bbox, int metric,
+                       int compute_aos, const int32_t *sweep_cd, const double *sweep_min_overlap, const double *thresholds,
+                       const int32_t *n_thresholds, int n_sweeps, int total_gt, int total_dt, int64_t *pr_counts,
+                       double *pr_sim, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+
 /* Diagnostic (csrc/diag.hip; replaces nothing in the reference): the matrix pipe's sustained rate on THIS part under its socket power
  * cap -- `blocks` workgroups of four waves, each wave `iters` x 16 v_mfma_f32_16x16x32_f16 on register operands (a 64 x 64 x 32 tile
  * step), nothing else in the loop. a_operands / b_operands: 512 x 16 bytes of fp16 values each (what the operand DATA is matters: the
