@@ -150,6 +150,13 @@ SIGNATURES = {
     "cpd_kitti_match_pr": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _I,
                                 _I, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_adam_step": (_I, [_VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _I, _F, _VP, _VP]),
+    "cpd_outline_ground_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_outline_ground": (_I, [_VP, _I, _I, _VP, _I, _I, _FP, _D, ctypes.POINTER(_D), ctypes.POINTER(_D), _I, _VP, _VP, _VP,
+                                _VP, _VP, _SZ, _VP]),
+    "cpd_outline_dbscan_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_outline_dbscan": (_I, [_VP, _VP, _VP, _I, _I, _D, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_outline_boxes_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_outline_boxes": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, ctypes.POINTER(_D), _I, _VP, _VP, _SZ, _VP]),
 }
 
 

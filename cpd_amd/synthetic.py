@@ -236,3 +236,133 @@ def _kitti_dict(a):
         else:
             out[k] = np.array(v, dtype=np.float64)
     return out
+
+
+# ---- pseudo-label scene (cpd_amd.outline) --------------------------------------------------------------------------------
+
+def _ray_obb(d, sensor_z, c, size, yaw):
+    """Entry distance of unit rays d [R, 3] from (0, 0, sensor_z) into the box (centre c, size (l, w, h), heading yaw); inf
+    where missed (slab test in the box frame)."""
+    cs, sn = np.cos(-yaw), np.sin(-yaw)
+    o = np.array([-c[0], -c[1], sensor_z - c[2]])
+    o = np.array([cs * o[0] - sn * o[1], sn * o[0] + cs * o[1], o[2]])
+    db = np.stack([cs * d[:, 0] - sn * d[:, 1], sn * d[:, 0] + cs * d[:, 1], d[:, 2]], -1)
+    half = np.asarray(size, np.float64) / 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t1 = (-half - o) / db
+        t2 = (half - o) / db
+    t1 = np.where(np.isnan(t1), -np.inf, t1)
+    t2 = np.where(np.isnan(t2), np.inf, t2)
+    tn = np.minimum(t1, t2).max(1)
+    tf = np.maximum(t1, t2).min(1)
+    return np.where((tn <= tf) & (tn > 0.5), tn, np.inf)
+
+
+def outline_scene(seed=0, dtype=np.float16, n_az=2650, n_vehicles=14, n_pedestrians=10, n_cyclists=6, n_clutter=10):
+    """A Waymo-shape frame for the pseudo-label generator (cpd_amd.outline): the waymo_cloud beam pattern (64 beams,
+    -17.6..+2.4 deg, sensor 2 m above z = 0, 75 m range, 2 cm range noise) ray-cast against
+      * ground with N(0, 2 cm) height noise and one sloped sector (azimuth 1.0..1.6 rad, rising 8 % beyond 15 m), so the
+        ground fit breaks, restarts and skips bin gaps;
+      * oriented boxes sized inside the config's Vehicle / Pedestrian / Cyclist ranges, low clutter 0.3..0.6 m high, one
+        tall structure (8 m) and the waymo_cloud ring of 12 buildings.
+    Returns [N, 5] of `dtype` (float16, as Waymo frames are saved, or float32): x, y, z, intensity, elongation.
+    Points whose ground segment index would change under +-2 float32 ulp of atan2 are rotated about z in small steps until
+    it does not (atan2 is the one projection op that is not reproducible bit for bit across libraries)."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.float16, np.float32):
+        raise TypeError("outline_scene: float16 or float32")
+    rng = np.random.default_rng(seed + 7000)
+    sensor_z = 2.0
+    elev = np.deg2rad(np.linspace(-17.6, 2.4, 64))
+    az = np.linspace(0.0, 2 * np.pi, n_az, endpoint=False) + rng.uniform(0, 2 * np.pi / n_az)
+    e, a = np.meshgrid(elev, az, indexing="ij")
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], -1).reshape(-1, 3)
+    ce, dz = np.cos(e).reshape(-1), d[:, 2]
+    azr = np.mod(a.reshape(-1), 2 * np.pi)
+    # ground: flat z = 0, or z = s * (r - r0) in the sloped sector beyond r0
+    t_flat = np.where(dz < -1e-6, -sensor_z / np.minimum(dz, -1e-6), np.inf)
+    s, r0 = 0.08, 15.0
+    sector = (azr > 1.0) & (azr < 1.6)
+    with np.errstate(divide="ignore"):
+        t_slope = (sensor_z + s * r0) / (s * ce - dz)
+    slope_ok = sector & (t_slope > 0) & (t_slope * ce > r0)
+    t_ground = np.where(slope_ok, t_slope, t_flat)
+    t_best, is_ground = t_ground.copy(), np.isfinite(t_ground)
+
+    def place(n, lo_r, hi_r):
+        r = rng.uniform(lo_r, hi_r, n)
+        ang = rng.uniform(0, 2 * np.pi, n)
+        ang = np.where((ang > 0.9) & (ang < 1.7), ang + 1.0, ang)   # objects stay off the sloped sector
+        return np.stack([r * np.cos(ang), r * np.sin(ang)], -1)
+
+    objs = []
+    for n, (l0, l1), (w0, w1), (h0, h1), rr in [(n_vehicles, (3.6, 5.2), (1.7, 2.2), (1.4, 2.1), (6, 55)),
+                                                (n_pedestrians, (0.5, 0.8), (0.4, 0.7), (1.5, 1.9), (5, 35)),
+                                                (n_cyclists, (1.6, 2.1), (0.6, 0.9), (1.5, 1.9), (5, 40)),
+                                                (n_clutter, (0.6, 1.5), (0.5, 1.2), (0.3, 0.6), (5, 30)),
+                                                (1, (3.0, 4.0), (3.0, 4.0), (8.0, 8.0), (20, 30))]:
+        for xy in place(n, *rr):
+            size = (rng.uniform(l0, l1), rng.uniform(w0, w1), rng.uniform(h0, h1))
+            objs.append((np.array([xy[0], xy[1], size[2] / 2]), size, rng.uniform(-np.pi, np.pi)))
+    for k in range(12):
+        ang = 2 * np.pi * k / 12
+        size = (rng.uniform(8, 14), rng.uniform(8, 14), rng.uniform(6, 14))
+        objs.append((np.array([62 * np.cos(ang), 62 * np.sin(ang), size[2] / 2]), size, ang))
+    for c, size, yaw in objs:
+        t = _ray_obb(d, sensor_z, c, size, yaw)
+        closer = t < t_best
+        t_best = np.where(closer, t, t_best)
+        is_ground &= ~closer
+    hit = np.isfinite(t_best) & (t_best < 75.0)
+    t = t_best[hit] + rng.normal(0, 0.02, hit.sum())
+    pts = d[hit] * t[:, None]
+    pts[:, 2] += sensor_z
+    g = is_ground[hit]
+    pts[g, 2] += rng.normal(0, 0.02, g.sum())
+    pts = pts.astype(dtype)
+    pts = _settle_segments(pts, dtype)
+    out = np.empty((pts.shape[0], 5), dtype)
+    out[:, :3] = pts
+    out[:, 3] = rng.uniform(0, 1, pts.shape[0])
+    out[:, 4] = rng.uniform(0, 1, pts.shape[0])
+    return out
+
+
+def outline_segment(angle32, dtype):
+    """seg = int32(floor((atan2 + pi) / (2 pi / 150))) in `dtype` arithmetic from a float32 atan2 value (the reference's
+    Processor.project_5D under numpy's per-op rounding; float16 ops compute in float32 and round)."""
+    dtype = np.dtype(dtype)
+    a = np.asarray(angle32, np.float32).astype(dtype)
+    pi_t, step_t = dtype.type(np.pi), dtype.type(2 * np.pi / 150)
+    if dtype == np.float16:
+        s = (a.astype(np.float32) + np.float32(pi_t)).astype(np.float16)
+        q = (s.astype(np.float32) / np.float32(step_t)).astype(np.float16)
+    else:
+        q = (a + pi_t) / step_t
+    return np.floor(q).astype(np.int32)
+
+
+def _settle_segments(pts, dtype, ulps=2):
+    moved = 0
+    for _ in range(64):
+        x, y = pts[:, 0].astype(np.float32), pts[:, 1].astype(np.float32)
+        a = np.arctan2(y, x)
+        segs = [outline_segment(a, dtype)]
+        lo = hi = a
+        for _k in range(ulps):
+            lo, hi = np.nextafter(lo, np.float32(-np.inf)), np.nextafter(hi, np.float32(np.inf))
+            segs += [outline_segment(lo, dtype), outline_segment(hi, dtype)]
+        bad = np.zeros(len(pts), bool)
+        for sg in segs[1:]:
+            bad |= sg != segs[0]
+        if not bad.any():
+            break
+        moved += int(bad.sum())
+        rot = 2e-3
+        xb, yb = pts[bad, 0].astype(np.float64), pts[bad, 1].astype(np.float64)
+        pts[bad, 0] = (np.cos(rot) * xb - np.sin(rot) * yb).astype(dtype)
+        pts[bad, 1] = (np.sin(rot) * xb + np.cos(rot) * yb).astype(dtype)
+    else:
+        raise RuntimeError("outline_scene: could not settle segment indices")
+    _settle_segments.last_moved = moved
+    return pts

@@ -825,6 +825,39 @@ int cpd_kitti_match_pr(const double *overlaps, const int64_t *pair_off, const in
 double cpd_mfma_burn_flops(int blocks, int iters);
 int cpd_mfma_burn(const void *a_operands, const void *b_operands, float *sink, int blocks, int iters, cpd_stream_t stream);
 
+/* ---- DBSCAN pseudo-label generator (csrc/outline.hip): cpd/unsupervised_core/outline_utils.py OutlineFitter.remove_ground /
+ * clustering / box_fit (l.542-576, 789-846, 609-701, 761-787) and ground_removal.py Processor / Segmentation (l.60-242) for a
+ * batch of frames. frame_off is a DEVICE int32 array [n_frames + 1] of row offsets (n_points = frame_off[n_frames]). No host
+ * synchronisation and no allocation inside a call. */
+size_t cpd_outline_ground_workspace_bytes(int n_frames, int n_points);
+/* remove_ground: points [n_points][row_stride] float16 (is_half = 1) or float32, x y z in the first three columns. consts =
+ * (pi, 2 pi / 150, 0.3, 149.7 / 150, ground_max_threshold) rounded to the input dtype; thr [n_bands] = ground_min_threshold, dist [7] =
+ * ground_min_distance padded (entries 0 .. max(1, n_bands - 1) are read; they must not decrease from entry 1 on), 1 <= n_bands
+ * <= 6. Frame f's non-ground points go to out_xyz [n_points][3] / out_src (row within the frame) at rows frame_off[f] ..
+ * frame_off[f] + out_count[f], in the canonical order (distance bands; in a band the high points in input order, then the low
+ * points by segment, input order within a segment). *err |= 1 when a segment index falls outside the table (not expected). */
+int cpd_outline_ground(const void *points, int is_half, int row_stride, const int32_t *frame_off, int n_frames, int n_points,
+                       const float consts[5], double sensor_height, const double *thr, const double *dist, int n_bands,
+                       float *out_xyz, int32_t *out_src, int32_t *out_count, int32_t *err, void *workspace,
+                       size_t workspace_bytes, cpd_stream_t stream);
+size_t cpd_outline_dbscan_workspace_bytes(int n_frames, int n_points);
+/* sklearn.cluster.DBSCAN(eps, min_samples).fit(xyz).labels_ per frame (clustering, l.789-807): frame f = rows frame_off[f] ..
+ * frame_off[f] + frame_count[f] (DEVICE [n_frames]) of xyz [n_points][3] float32, neighbours by float64
+ * (dx*dx + dy*dy) + dz*dz <= eps*eps. labels [n_points] (-1 noise and padding rows), n_clusters [n_frames]. n_frames <= 1023. */
+int cpd_outline_dbscan(const float *xyz, const int32_t *frame_off, const int32_t *frame_count, int n_frames, int n_points,
+                       double eps, int min_samples, int32_t *labels, int32_t *n_clusters, void *workspace,
+                       size_t workspace_bytes, cpd_stream_t stream);
+size_t cpd_outline_boxes_workspace_bytes(int n_frames, int n_points);
+/* box_fit over the clusters of cpd_outline_dbscan's labels (rows as there): with apply_cluster_filter the clustering filter
+ * (size > cluster_min_points, max z < discard_max_height) first. params = (cluster_min_points, discard_max_height,
+ * min_box_volume, min_box_height, max_box_volume, max_box_len, ground_min_threshold[0], ground_min_distance[1]). Every hull
+ * edge is a candidate angle (the reference omits the closing edge). out [n_frames + 8 * box_cap] float64: box
+ * counts per frame, then the boxes frame by frame in cluster order, each [x y z dx dy dz heading, cluster number]; boxes past
+ * box_cap are counted but not written. */
+int cpd_outline_boxes(const float *xyz, const int32_t *frame_off, const int32_t *frame_count, int n_frames, int n_points,
+                      const int32_t *labels, const int32_t *n_clusters, int apply_cluster_filter, const double params[8],
+                      int box_cap, double *out, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
