@@ -13,7 +13,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import layer_table, ops
 from ._lib import check, farr, lib, ptr, stream
 
 
@@ -458,26 +458,18 @@ class AnchorHeadSingleV2(AnchorHeadSingle):
         c = self.SHARD_C
 
         def kio(w):                                                  # (Cout, Cin, k, k) -> [k*k, Cin, Cout]
-            return w.permute(2, 3, 1, 0).reshape(w.shape[2] * w.shape[3], w.shape[1], w.shape[0]).contiguous()
+            return layer_table.conv2d_kio(w).contiguous()
 
         f = {}
         s, t = _fold_bn(sd, "shared_conv.1", 1e-5, sd["shared_conv.0.bias"])
         f["shared"] = (ops.pack_weight(kio(sd["shared_conv.0.weight"]).to(dev)), s.to(dev), t.to(dev), sd["shared_conv.0.weight"].shape[1], c)
-        w1, s1, t1 = [], [], []
-        outs = [sd[b + ".3.weight"].shape[0] for b in self.BRANCHES]
-        w2 = torch.zeros(1, c * len(self.BRANCHES), sum(outs))
-        b2 = torch.zeros(sum(outs))
-        col = 0
-        for i, b in enumerate(self.BRANCHES):
-            w1.append(kio(sd[b + ".0.weight"]))
-            s, t = _fold_bn(sd, b + ".1", 1e-5, sd[b + ".0.bias"])
-            s1.append(s); t1.append(t)
-            w2[0, i * c:(i + 1) * c, col:col + outs[i]] = sd[b + ".3.weight"].reshape(outs[i], c).t()
-            b2[col:col + outs[i]] = sd[b + ".3.bias"]
-            col += outs[i]
-        f["first"] = (ops.pack_weight(torch.cat(w1, dim=2).to(dev)), torch.cat(s1).to(dev), torch.cat(t1).to(dev), c, c * len(self.BRANCHES))
-        f["second"] = (ops.pack_weight(w2.to(dev)), None, b2.to(dev), c * len(self.BRANCHES), sum(outs))
-        f["n_cls"] = outs[0]
+        folds = [_fold_bn(sd, b + ".1", 1e-5, sd[b + ".0.bias"]) for b in self.BRANCHES]
+        w1, s1, t1, w2, b2, slices = layer_table.fuse_branches(
+            [kio(sd[b + ".0.weight"]) for b in self.BRANCHES], [s for s, _ in folds], [t for _, t in folds],
+            [kio(sd[b + ".3.weight"]) for b in self.BRANCHES], [sd[b + ".3.bias"] for b in self.BRANCHES])
+        f["first"] = (ops.pack_weight(w1.to(dev)), s1.to(dev), t1.to(dev), c, w1.shape[2])
+        f["second"] = (ops.pack_weight(w2.to(dev)), None, b2.to(dev), w2.shape[1], w2.shape[2])
+        f["n_cls"] = slices[0][1]
         if self.conv_dir_cls is not None:
             wd = sd["conv_dir_cls.weight"]
             f["dir"] = (ops.pack_weight(kio(wd).to(dev)), None, sd["conv_dir_cls.bias"].to(dev), wd.shape[1], wd.shape[0])

@@ -11,11 +11,12 @@ Weights come in under the reference's own state_dict names (so a CPD checkpoint 
 import contextlib
 import math
 from dataclasses import dataclass, field
-from typing import Dict, List
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, layer_table, ops, train_ops
+from .layer_table import _DOWN, STRIDED_STAGES, final_shape      # noqa: F401  (_DOWN: importable from here as before)
 
 
 @dataclass
@@ -116,92 +117,27 @@ class ModelConfig:
         return self.num_class if name == "hm" else self.head_channels[name]
 
 
-# Sparse stages of VoxelResBackBone8x (spconv_backbone.py:414-455): (name, ksize, stride, pad)
-_DOWN = {
-    "conv2": ([3, 3, 3], [2, 2, 2], [1, 1, 1]),
-    "conv3": ([3, 3, 3], [2, 2, 2], [1, 1, 1]),
-    "conv4": ([3, 3, 3], [2, 2, 2], [0, 1, 1]),
-    "conv_out": ([3, 1, 1], [2, 1, 1], [0, 0, 0]),
-}
-
-
 def init_state_dict(cfg: ModelConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Random-init weights under the REFERENCE's state_dict names and layouts (spconv-2.x conv
     weights (Cout,kD,kH,kW,Cin); torch Conv2d / ConvTranspose2d / BatchNorm). BN statistics are
     non-trivial so that folding errors would show up in parity tests."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
-
-    def conv3d(name, cin, cout, k, bias):
-        fan = cin * k[0] * k[1] * k[2]
-        sd[name + ".weight"] = torch.randn(cout, k[0], k[1], k[2], cin, generator=g) * math.sqrt(2.0 / fan)
-        if bias:
-            sd[name + ".bias"] = torch.randn(cout, generator=g) * 0.05
-
-    def bn(name, c):
-        sd[name + ".weight"] = torch.rand(c, generator=g) * 0.5 + 0.75
-        sd[name + ".bias"] = torch.randn(c, generator=g) * 0.1
-        sd[name + ".running_mean"] = torch.randn(c, generator=g) * 0.1
-        sd[name + ".running_var"] = torch.rand(c, generator=g) * 0.5 + 0.75
-        sd[name + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
-
-    def conv2d(name, cin, cout, k, bias, transposed=False):
-        fan = cin * k * k
-        shape = (cin, cout, k, k) if transposed else (cout, cin, k, k)
-        sd[name + ".weight"] = torch.randn(*shape, generator=g) * math.sqrt(2.0 / fan)
-        if bias:
-            sd[name + ".bias"] = torch.randn(cout, generator=g) * 0.05
-
-    nf = cfg.num_filters
-    p = "backbone_3d."
-    conv3d(p + "conv_input.0", cfg.num_point_features, nf[0], [3, 3, 3], False)
-    bn(p + "conv_input.1", nf[0])
-
-    def basic_block(name, c):
-        conv3d(name + ".conv1", c, c, [3, 3, 3], True)
-        bn(name + ".bn1", c)
-        conv3d(name + ".conv2", c, c, [3, 3, 3], True)
-        bn(name + ".bn2", c)
-
-    basic_block(p + "conv1.0", nf[0])
-    basic_block(p + "conv1.1", nf[0])
-    for lvl, stage in enumerate(["conv2", "conv3", "conv4"], start=1):
-        k = _DOWN[stage][0]
-        conv3d(p + stage + ".0.0", nf[lvl - 1], nf[lvl], k, False)
-        bn(p + stage + ".0.1", nf[lvl])
-        basic_block(p + stage + ".1", nf[lvl])
-        basic_block(p + stage + ".2", nf[lvl])
-    conv3d(p + "conv_out.0", nf[3], cfg.out_features, _DOWN["conv_out"][0], False)
-    bn(p + "conv_out.1", cfg.out_features)
-
-    # BaseBEVBackbone (base_bev_backbone.py:27-59)
-    p = "backbone_2d."
     depth = 2  # sparse_shape z after conv_out for a 41-deep input; generic value computed by engine
-    c_in_list = [cfg.out_features * depth] + cfg.bev_num_filters[:-1]
-    for lvl in range(len(cfg.bev_layer_nums)):
-        c = cfg.bev_num_filters[lvl]
-        conv2d(p + "blocks.%d.1" % lvl, c_in_list[lvl], c, 3, False)
-        bn(p + "blocks.%d.2" % lvl, c)
-        for k in range(cfg.bev_layer_nums[lvl]):
-            conv2d(p + "blocks.%d.%d" % (lvl, 4 + 3 * k), c, c, 3, False)
-            bn(p + "blocks.%d.%d" % (lvl, 5 + 3 * k), c)
-        u = cfg.bev_upsample_strides[lvl]
-        conv2d(p + "deblocks.%d.0" % lvl, c, cfg.bev_num_upsample_filters[lvl], u, False, transposed=True)
-        bn(p + "deblocks.%d.1" % lvl, cfg.bev_num_upsample_filters[lvl])
-
-    # CenterHead (center_head.py:73-94, SeparateHead l.11-45; USE_BIAS_BEFORE_NORM True)
-    p = "dense_head."
-    c_cat = sum(cfg.bev_num_upsample_filters)
-    sc = cfg.shared_conv_channel
-    conv2d(p + "shared_conv.0", c_cat, sc, 3, True)
-    bn(p + "shared_conv.1", sc)
-    for name in cfg.head_names():
-        q = p + "heads_list.0.%s." % name
-        conv2d(q + "0.0", sc, sc, 3, True)
-        bn(q + "0.1", sc)
-        conv2d(q + "1", sc, cfg.head_out(name), 3, True)
-        if name == "hm":
-            sd[q + "1.bias"] = torch.full((cfg.num_class,), -2.19)   # center_head.py:30
+    for L in layer_table.centerpoint_layers(cfg, depth=depth):
+        fan = L.c_in * math.prod(L.ksize)
+        sd[L.conv + ".weight"] = torch.randn(*L.weight_shape(), generator=g) * math.sqrt(2.0 / fan)
+        if L.bias:
+            sd[L.conv + ".bias"] = torch.randn(L.c_out, generator=g) * 0.05
+        if L.bn:
+            c = L.c_out
+            sd[L.bn + ".weight"] = torch.rand(c, generator=g) * 0.5 + 0.75
+            sd[L.bn + ".bias"] = torch.randn(c, generator=g) * 0.1
+            sd[L.bn + ".running_mean"] = torch.randn(c, generator=g) * 0.1
+            sd[L.bn + ".running_var"] = torch.rand(c, generator=g) * 0.5 + 0.75
+            sd[L.bn + ".num_batches_tracked"] = torch.tensor(0, dtype=torch.long)
+        if L.slot == ("head", "hm", 1):
+            sd[L.conv + ".bias"] = torch.full((cfg.num_class,), -2.19)   # center_head.py:30
     return sd
 
 
@@ -228,12 +164,111 @@ class _Layer:
         self.relu = relu
 
 
+class StridedStageChain:
+    """The INDEX CHAIN of the four strided stages (output set -> row order -> rulebooks: 6-8 small launches and one count read-back per
+    stage), which depends on site lists only, never on features. With a side stream it runs on a second HIP stream, ahead of the
+    convolutions, and PIPELINED: a stage's output set is marked and counted (conv_outset_begin) as soon as the list it is marked from
+    exists -- stage 2's at the start of the step, before the level-0 index, rulebook and the level-1 convs are queued; stage k + 1's as
+    soon as stage k's list is emitted -- so that by the time the host asks for a count (conv_outset_end) the side stream has it, and the
+    host is never away from the main stream for long. The index kernels overlap convolutions that do not fill the chip (one frame: 0.6
+    of 3.0 ms of kernel time is index work). Without one: the same calls in the same order on the current stream. Same kernels, same
+    results.
+
+    The owner's `tables(stage, in_coords, in_index, in_shape, out_idx, out_index, out_shape)` builds what it needs of a stage (row
+    order, rulebooks) and returns it; use: start() -> [level-0 index] -> index_ready() -> [level-1 convs] -> next() per stage, each
+    after the previous stage's convs are queued (the count read-back inside can still block the host for a moment, and the main
+    stream should have its work by then).
+
+    Allocator safety across the streams: side-stream tensors read on the main stream (tables, lists, indexes) and main-stream
+    tensors read on the side stream are held in `keep`, i.e. until the owner drops this chain for the NEXT step's -- and that one's
+    start() makes the side stream wait for everything queued on the main stream so far: the caching allocator can hand a freed
+    block to the other stream only after its readers ran."""
+
+    def __init__(self, tables, batch, device, side_stream):
+        self.tables, self.batch = tables, batch
+        self.side = _lib.side_stream(device, "index") if side_stream else None     # (per current stream: an engine may be driven from several streams over its life)
+        self.main = torch.cuda.current_stream(device) if side_stream else None
+        self.keep = []
+        self._stage = 0
+        self._pending = self._after = None
+
+    def _begin(self, coords, shape):
+        return ops.conv_outset_begin(coords, self.batch, shape, *_DOWN[STRIDED_STAGES[self._stage]])
+
+    def start(self, coords, shape):
+        """level 0's site list exists: with a side stream, stage 2's output set is marked and counted beside what the main stream does next"""
+        self._level = (coords, None, shape)
+        if self.side is not None:
+            self.side.wait_event(self.main.record_event())
+            with torch.cuda.stream(self.side):
+                self._pending = self._begin(coords, shape)
+
+    def index_ready(self, index):
+        """the level-0 site index (and its row order) is complete at this point of the main stream"""
+        self._level = (self._level[0], index, self._level[2])
+        self._after = self.main.record_event() if self.side is not None else None
+
+    def next(self):
+        """Queue the next stage's chain -- its conv_outset_end, the following stage's conv_outset_begin, the owner's tables -- and make
+        the main stream wait for it. Returns what `tables` returned."""
+        coords, index, shape = self._level
+        if self._pending is None:                              # (no side stream: the first output set is marked here, after the level-1 convs)
+            self._pending = self._begin(coords, shape)
+        stage = STRIDED_STAGES[self._stage]
+        with (torch.cuda.stream(self.side) if self.side is not None else contextlib.nullcontext()):
+            out_idx, out_index, out_shape = ops.conv_outset_end(self._pending)
+            if self._after is not None:
+                self.side.wait_event(self._after)
+                self._after = None
+            self._stage += 1
+            # (marked from the canonical list, whatever row order the owner gives the level)
+            self._pending = self._begin(out_idx, out_shape) if self._stage < len(STRIDED_STAGES) else None
+            T = self.tables(stage, coords, index, shape, out_idx, out_index, out_shape)
+            if self.side is not None:
+                self.main.wait_event(self.side.record_event())
+        self.keep.append((self._level, self._pending, T))
+        self._level = (out_idx, out_index, out_shape)
+        return T
+
+
+def bev_tables(cache, batch, h, w, device, transposed=False):
+    """The pixel tables of BaseBEVBackbone's convs over (batch, h, w) maps, built once per shape; `transposed`: the stride-2 conv's
+    transposed table as well (its input gradient)."""
+    key = (batch, h, w)
+    if key not in cache:
+        t = {}
+        t["s1"] = ops.rulebook_conv2d(batch, h, w, 3, 3, 1, 1, device)
+        t["s2"] = ops.rulebook_conv2d(batch, h, w, 3, 3, 2, 1, device)
+        h2, w2 = t["s2"][1], t["s2"][2]
+        if transposed:
+            t["s2_t"] = train_ops.rulebook_conv2d_transpose(batch, h, w, 3, 3, 2, 1, device)
+        t["s1_half"] = ops.rulebook_conv2d(batch, h2, w2, 3, 3, 1, 1, device)
+        # ConvTranspose2d(k=s=2) destination rows: tap (a,b) of coarse pixel (y,x) -> (2y+a, 2x+b)
+        b_i = torch.arange(batch, device=device).view(-1, 1, 1)
+        yy = torch.arange(h2, device=device).view(1, -1, 1)
+        xx = torch.arange(w2, device=device).view(1, 1, -1)
+        maps = [((b_i * h + 2 * yy + a) * w + 2 * xx + bb).reshape(-1) for a in range(2) for bb in range(2)]
+        t["up2"] = torch.stack(maps).to(torch.int32).contiguous()
+        cache[key] = t
+    return cache[key]
+
+
+class _StageTables(NamedTuple):
+    """a strided stage's tables, as the engine's convs read them"""
+    out_idx: torch.Tensor      # the level's site list in its row order
+    out_index: object
+    out_shape: list
+    nbr_dn: torch.Tensor
+    nbr: Optional[torch.Tensor]
+    pairs_out: bool
+    canon: Optional[tuple]     # (held: the chunk-wise tables were built from it)
+
+
 class CenterPointEngine:
     """points [N, C] (device f32)  ->  {'pred_boxes','pred_scores','pred_labels'} per frame."""
 
-    SPARSE_BN_EPS = 1e-3   # spconv_backbone.py:410
-    BEV_BN_EPS = 1e-3      # base_bev_backbone.py:38
-    HEAD_BN_EPS = 1e-5     # nn.BatchNorm2d default, center_head.py:24,78
+    # BatchNorm eps: spconv_backbone.py:410, base_bev_backbone.py:38, nn.BatchNorm2d's default (center_head.py:24,78)
+    BN_EPS = {"sparse": 1e-3, "bev": 1e-3, "head": 1e-5}
 
     def __init__(self, cfg: ModelConfig, state_dict: Dict[str, torch.Tensor], device="cuda", host_results=False):
         self.cfg = cfg
@@ -246,108 +281,44 @@ class CenterPointEngine:
                                        cfg.max_points_per_voxel, cfg.max_voxels, device=self.device)
         self._voxelizers = [self.voxelizer]
         self._group_voxelizers = []
-        self._build_sparse()
         self._bev_cache = {}
-        self._build_dense()
+        self._build_layers()
 
     # ------------------------------------------------------------------ weights
-    def _sparse_w(self, name):
-        w = self.sd[name + ".weight"]                     # (Cout, kD, kH, kW, Cin)
-        cout, cin = w.shape[0], w.shape[-1]
-        return w.reshape(cout, -1, cin).permute(1, 2, 0)   # [kv, Cin, Cout]
+    def _folded(self, L):
+        """a layer_table record -> (w_kio, scale, shift): the reference's weights in our layout, eval BatchNorm (+ conv bias) folded"""
+        sd = self.sd
+        w = L.kio(sd[L.conv + ".weight"], self.cfg.out_features, self._final_shape()[0])
+        bias = sd.get(L.conv + ".bias") if L.bias else None
+        if L.bn is None:
+            return w, None, bias
+        s, t = _fold_bn(sd, L.bn, self.BN_EPS[L.group], bias)
+        return w, s.repeat(L.up * L.up), t.repeat(L.up * L.up)      # (a deblock's u*u taps are column groups of one GEMM)
 
-    def _build_sparse(self):
-        sd, dev, eps = self.sd, self.device, self.SPARSE_BN_EPS
-        p = "backbone_3d."
-        L = {}
-        s, t = _fold_bn(sd, p + "conv_input.1", eps)
-        L["conv_input"] = _Layer(self._sparse_w(p + "conv_input.0"), s, t, True, dev)
-
-        def block(name):
-            s1, t1 = _fold_bn(sd, name + ".bn1", eps, sd.get(name + ".conv1.bias"))
-            s2, t2 = _fold_bn(sd, name + ".bn2", eps, sd.get(name + ".conv2.bias"))
-            return (_Layer(self._sparse_w(name + ".conv1"), s1, t1, True, dev),
-                    _Layer(self._sparse_w(name + ".conv2"), s2, t2, True, dev))   # relu after the residual add
-
-        L["conv1"] = [block(p + "conv1.0"), block(p + "conv1.1")]
-        for stage in ["conv2", "conv3", "conv4"]:
-            s, t = _fold_bn(sd, p + stage + ".0.1", eps)
-            L[stage + ".down"] = _Layer(self._sparse_w(p + stage + ".0.0"), s, t, True, dev)
-            L[stage] = [block(p + stage + ".1"), block(p + stage + ".2")]
-        s, t = _fold_bn(sd, p + "conv_out.1", eps)
-        L["conv_out"] = _Layer(self._sparse_w(p + "conv_out.0"), s, t, True, dev)
-        self.sparse = L
-
-    def _build_dense(self):
-        cfg, sd, dev = self.cfg, self.sd, self.device
-        p = "backbone_2d."
-        depth = self._final_depth()
-        C = cfg.out_features
-        self.bev_levels = []
-        for lvl in range(len(cfg.bev_layer_nums)):
-            convs = []
-            names = ["blocks.%d.1" % lvl] + ["blocks.%d.%d" % (lvl, 4 + 3 * k) for k in range(cfg.bev_layer_nums[lvl])]
-            bns = ["blocks.%d.2" % lvl] + ["blocks.%d.%d" % (lvl, 5 + 3 * k) for k in range(cfg.bev_layer_nums[lvl])]
-            for i, (cn, bnn) in enumerate(zip(names, bns)):
-                w = sd[p + cn + ".weight"]                                   # (Cout, Cin, 3, 3)
-                if lvl == 0 and i == 0:
-                    # reference channel = c*D + z (height_compression.py:136-138); ours = z*C + c
-                    cout = w.shape[0]
-                    w = w.reshape(cout, C, depth, 3, 3).permute(0, 2, 1, 3, 4).reshape(cout, depth * C, 3, 3)
-                s, t = _fold_bn(sd, p + bnn, self.BEV_BN_EPS)
-                convs.append(_Layer(w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]), s, t, True, dev))
-            u = cfg.bev_upsample_strides[lvl]
-            wd = sd[p + "deblocks.%d.0.weight" % lvl]                        # (Cin, Cout, u, u)
-            s, t = _fold_bn(sd, p + "deblocks.%d.1" % lvl, self.BEV_BN_EPS)
-            cin, cout = wd.shape[0], wd.shape[1]
-            # ConvTranspose2d(k=s=u) = one 1x1 GEMM with the u*u taps stacked along the columns
-            w_kio = wd.permute(0, 2, 3, 1).reshape(1, cin, u * u * cout)
-            de = _Layer(w_kio, s.repeat(u * u), t.repeat(u * u), True, dev)
-            self.bev_levels.append((convs, de, u, cout))
+    def _build_layers(self):
+        at = {L.slot: _Layer(*self._folded(L), L.relu, self.device) for L in layer_table.centerpoint_layers(self.cfg) if L.group != "head"}
+        self.sparse, self.bev_levels = layer_table.sparse_and_bev(self.cfg, at)
         self._build_head()
 
     def _build_head(self):
         """CenterHead's convolutions (center_head.py:73-94); a subclass with another dense head (cpd_amd/anchor_engine.py) overrides this,
         `_head_rows` and `decode_and_nms`."""
-        cfg, sd, dev = self.cfg, self.sd, self.device
-        p = "dense_head."
-        s, t = _fold_bn(sd, p + "shared_conv.1", self.HEAD_BN_EPS, sd.get(p + "shared_conv.0.bias"))
-        w = sd[p + "shared_conv.0.weight"]
-        self.shared = _Layer(w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]), s, t, True, dev)
+        first, last = [], []
+        for L in layer_table.centerpoint_layers(self.cfg):
+            if L.slot == ("shared",):
+                self.shared = _Layer(*self._folded(L), L.relu, self.device)
+            elif L.slot[0] == "head":
+                (last if L.slot[2] else first).append(self._folded(L))
         # the five SeparateHead branches: first convs fused along Cout, second convs block-diagonal
-        names = cfg.head_names()
-        sc = cfg.shared_conv_channel
-        w1, s1, t1 = [], [], []
-        n_out = sum(cfg.head_out(n) for n in names)
-        w2 = torch.zeros(9, sc * len(names), n_out)
-        b2 = torch.zeros(n_out)
-        self.head_slices = {}
-        col = 0
-        for hi, name in enumerate(names):
-            q = p + "heads_list.0.%s." % name
-            w = sd[q + "0.0.weight"]
-            w1.append(w.permute(2, 3, 1, 0).reshape(9, sc, sc))
-            s, t = _fold_bn(sd, q + "0.1", self.HEAD_BN_EPS, sd.get(q + "0.0.bias"))
-            s1.append(s); t1.append(t)
-            wo = sd[q + "1.weight"]                                          # (co, sc, 3, 3)
-            co = wo.shape[0]
-            w2[:, hi * sc:(hi + 1) * sc, col:col + co] = wo.permute(2, 3, 1, 0).reshape(9, sc, co)
-            b2[col:col + co] = sd[q + "1.bias"]
-            self.head_slices[name] = (col, co)
-            col += co
-        self.head1 = _Layer(torch.cat(w1, dim=2), torch.cat(s1), torch.cat(t1), True, dev)
-        self.head2 = _Layer(w2, None, b2, False, dev)
-        self.head_ld = 16 * ((n_out + 15) // 16)
+        (lw, _, lb) = zip(*last)
+        w1, s1, t1, w2, b2, slices = layer_table.fuse_branches(*zip(*first), lw, lb)
+        self.head_slices = dict(zip(self.cfg.head_names(), slices))
+        self.head1 = _Layer(w1, s1, t1, True, self.device)
+        self.head2 = _Layer(w2, None, b2, False, self.device)
+        self.head_ld = 16 * ((w2.shape[2] + 15) // 16)
 
     def _final_shape(self):
-        shape = self.cfg.sparse_shape
-        for stage in ["conv2", "conv3", "conv4", "conv_out"]:
-            k, s, pd = _DOWN[stage]
-            shape = ops.conv_out_shape(shape, k, s, pd)
-        return shape
-
-    def _final_depth(self):
-        return self._final_shape()[0]
+        return final_shape(self.cfg)
 
     def _side_stream(self):
         return _lib.side_stream(self.device, "index")      # (per current stream: an engine may be driven from several streams over its life)
@@ -425,56 +396,14 @@ class CenterPointEngine:
         self.level_indexes = {}                               # name -> SiteIndex of the level (in the level's row order)
         L = self.sparse
         shape = self.cfg.sparse_shape
-        # The INDEX CHAIN of the strided stages (output set -> row order -> rulebooks: 6-8 small launches and one count read-back per
-        # stage) depends on site lists only, never on features. With `index_side_stream` it runs on a second HIP stream, ahead of the
-        # convolutions, and PIPELINED: a stage's output set is marked and counted (conv_outset_begin) as soon as the list it is marked
-        # from exists -- stage 2's right here, before the level-0 index, rulebook and the level-1 convs are queued; stage k + 1's as
-        # soon as stage k's list is emitted -- so that by the time the host asks for a count (conv_outset_end) the side stream has it,
-        # and the host is never away from the main stream for long. The index kernels overlap convolutions that do not fill the chip
-        # (one frame: 0.6 of 3.0 ms of kernel time is index work). Same kernels, same results.
-        side = self._side_stream() if (self.cfg.index_side_stream and feats.is_cuda and batch <= self.cfg.index_side_stream_max_frames) else None
-        main = torch.cuda.current_stream(self.device) if side is not None else None
-        stages = ["conv2", "conv3", "conv4", "conv_out"]
-        self._index_keep = []
+        side = self.cfg.index_side_stream and feats.is_cuda and batch <= self.cfg.index_side_stream_max_frames
 
-        def begin(stage, coords_c, shape):
+        def tables(stage, in_coords, index, in_shape, out_idx, out_index, out_shape):
+            """everything of a strided stage that depends on the site lists only: its row order and both rulebooks"""
             k, s, pd = _DOWN[stage]
-            return ops.conv_outset_begin(coords_c, batch, shape, k, s, pd)
-
-        if side is not None:
-            # side-stream tensors read on `main` (tables, lists, indexes) live until the NEXT step's chain starts, and that start waits
-            # for everything queued on `main` before this point: the caching allocator may hand a freed block to the side stream only
-            # after its readers ran
-            side.wait_event(main.record_event())
-            with torch.cuda.stream(side):
-                pending = begin(stages[0], coords, shape)
-        if index is None:
-            index = ops.SiteIndex.build(coords, batch, shape)
-        coords_c0, canon0 = coords, None
-        if canonical0 and self.cfg.row_order == "taps" and self.cfg.row_order_level0 and coords.shape[0] >= self.cfg.row_order_min_rows:
-            # level 0 in tap-pattern order too (round 4): its rows have 4.3 of 27 neighbours on average, and a canonical 16-row group
-            # executes 2.2x the (group, tap) pairs its rows need -- 1.3x after the sort (tools/unique_probe.py). `canonical0`: the
-            # voxelizer delivered canonical rows and a canonical index (rank = row), which is what the sort and the map need.
-            coords, n2o, o2n = ops.order_rows_by_taps(coords_c0, index, chunk_rows=self.cfg.row_order_chunk)
-            index.set_order(o2n)
-            feats = feats.index_select(0, n2o.long())
-            if self.cfg.chunked_rulebooks:
-                canon0 = (coords_c0, o2n, self.cfg.row_order_chunk)
-        pairs16 = pairs and self.cfg.pair_rows_level1
-
-        def tables(stage, index, pending, after=None):
-            """everything of a strided stage that depends on the site lists only: its output set (`pending`: its conv_outset_begin),
-            row order, both rulebooks -- and the next stage's conv_outset_begin; index = the site index of the stage's input level,
-            `after`: an event of the main stream that index is complete at"""
-            k, s, pd = _DOWN[stage]
-            out_idx, out_index, out_shape = ops.conv_outset_end(pending)
-            if after is not None:
-                torch.cuda.current_stream(self.device).wait_event(after)
             if stage == "conv_out":
-                return dict(out_idx=out_idx, out_c=out_idx, out_index=out_index, out_shape=out_shape,
-                            nbr_dn=ops.rulebook_conv(out_idx, index, k, s, pd), nbr=None, pairs_out=False, pending=None)
+                return _StageTables(out_idx, out_index, out_shape, ops.rulebook_conv(out_idx, index, k, s, pd), None, False, None)
             out_c = out_idx
-            pending = begin(stages[stages.index(stage) + 1], out_c, out_shape)     # (the canonical list: what the next output set is marked from)
             # "bricks" per level: only where the staged kernel is used (plan_channels: the widths it wins at); other levels keep "taps"
             c_lvl = L[stage + ".down"].c_out
             use_plan = self.cfg.plan_rulebooks and pairs and c_lvl in self.cfg.plan_channels
@@ -497,22 +426,24 @@ class CenterPointEngine:
             nbr = ops.rulebook_subm(out_idx, out_index, canonical=canon)
             if bricks and pairs_out and use_plan:
                 ops.rulebook_plan(nbr, self.cfg.plan_tile_rows)  # the level's four SubM convs: the staged row-wave kernel
-            return dict(out_idx=out_idx, out_c=out_c, out_index=out_index, out_shape=out_shape, nbr_dn=nbr_dn, nbr=nbr, pairs_out=pairs_out, canon=canon,
-                        pending=pending)
+            return _StageTables(out_idx, out_index, out_shape, nbr_dn, nbr, pairs_out, canon)
 
-        def stage_tables(stage, index, pending, after=None):
-            """queue a stage's index chain (on the side stream when there is one)"""
-            if side is None:
-                T = tables(stage, index, pending)
-                T["ev"] = None
-            else:
-                with torch.cuda.stream(side):
-                    T = tables(stage, index, pending, after)
-                    T["ev"] = side.record_event()
-            self._index_keep.append(T)
-            return T
-
-        ev_index = main.record_event() if side is not None else None          # the level-0 index (and its order) are complete here
+        chain = self._index_chain = StridedStageChain(tables, batch, self.device, side)     # (the previous step's is dropped here)
+        chain.start(coords, shape)
+        if index is None:
+            index = ops.SiteIndex.build(coords, batch, shape)
+        coords_c0, canon0 = coords, None
+        if canonical0 and self.cfg.row_order == "taps" and self.cfg.row_order_level0 and coords.shape[0] >= self.cfg.row_order_min_rows:
+            # level 0 in tap-pattern order too (round 4): its rows have 4.3 of 27 neighbours on average, and a canonical 16-row group
+            # executes 2.2x the (group, tap) pairs its rows need -- 1.3x after the sort (tools/unique_probe.py). `canonical0`: the
+            # voxelizer delivered canonical rows and a canonical index (rank = row), which is what the sort and the map need.
+            coords, n2o, o2n = ops.order_rows_by_taps(coords_c0, index, chunk_rows=self.cfg.row_order_chunk)
+            index.set_order(o2n)
+            feats = feats.index_select(0, n2o.long())
+            if self.cfg.chunked_rulebooks:
+                canon0 = (coords_c0, o2n, self.cfg.row_order_chunk)
+        pairs16 = pairs and self.cfg.pair_rows_level1
+        chain.index_ready(index)
         nbr = ops.rulebook_subm(coords, index, canonical=canon0)               # 'subm1' and 'res1' are the same L0 table
         self._range_reset()                                  # (the 5-channel input layer runs on the fp32 pipe: no block for `feats`)
         # level 1 (16 channels): with pair rows its layers run the K = 16 split-fp16 MFMA on 16-channel pair rows (three products of
@@ -530,50 +461,23 @@ class CenterPointEngine:
         levels = {"x_conv1": (export(x, pairs16, "x_conv1"), coords, shape)}
         self.level_indexes["x_conv1"] = index
         pairs_in = pairs16                 # (what conv2.down reads)
-        if side is None:
-            pending = begin(stages[0], coords_c0, shape)
-        # (a stage's chain is queued AFTER the previous stage's convs: its count read-back can still block the host for a moment, and
-        # the main stream should have its work by then)
-        T = stage_tables(stages[0], index, pending, after=ev_index)
-        for i, stage in enumerate(stages, start=2):
-            if T["ev"] is not None:
-                main.wait_event(T["ev"])
-            out_idx, out_shape = T["out_idx"], T["out_shape"]
+        T = chain.next()
+        for i, stage in enumerate(STRIDED_STAGES, start=2):
+            out_idx, out_shape = T.out_idx, T.out_shape
             if stage == "conv_out":
                 break
-            pairs_out = T["pairs_out"]
-            x = self._conv(L[stage + ".down"], x, T["nbr_dn"], out_idx.shape[0], in_pairs=pairs_in, out_pairs=pairs_out)
-            x = self._blocks(L[stage], x, T["nbr"], pairs=pairs_out)
+            pairs_out = T.pairs_out
+            x = self._conv(L[stage + ".down"], x, T.nbr_dn, out_idx.shape[0], in_pairs=pairs_in, out_pairs=pairs_out)
+            x = self._blocks(L[stage], x, T.nbr, pairs=pairs_out)
             pairs_in = pairs_out
             levels["x_conv%d" % i] = (export(x, pairs_in, "x_conv%d" % i), out_idx, out_shape)
-            self.level_indexes["x_conv%d" % i] = T["out_index"]
-            T = stage_tables(stages[i - 1], T["out_index"], T["pending"])
+            self.level_indexes["x_conv%d" % i] = T.out_index
+            T = chain.next()
         # (dense_pairs: the stride-8 output stays in pair rows -- densify is a copy of row bytes, so the BEV map it builds is a pair-row map)
-        x = self._conv(L["conv_out"], x, T["nbr_dn"], out_idx.shape[0], in_pairs=pairs_in, out_pairs=bool(dense_pairs) and pairs_in)
+        x = self._conv(L["conv_out"], x, T.nbr_dn, out_idx.shape[0], in_pairs=pairs_in, out_pairs=bool(dense_pairs) and pairs_in)
         self.encoded_pairs = bool(dense_pairs) and pairs_in
         self._rb_stage = "backbone"                            # the densified map inherits this output's range block
         return levels, (x, out_idx, out_shape)
-
-    def _bev_tables(self, batch, h, w):
-        key = (batch, h, w)
-        if key not in self._bev_cache:
-            dev = self.device
-            t = {}
-            t["s1"] = ops.rulebook_conv2d(batch, h, w, 3, 3, 1, 1, dev)
-            t["s2"] = ops.rulebook_conv2d(batch, h, w, 3, 3, 2, 1, dev)
-            h2, w2 = t["s2"][1], t["s2"][2]
-            t["s1_half"] = ops.rulebook_conv2d(batch, h2, w2, 3, 3, 1, 1, dev)
-            # ConvTranspose2d(k=s=2) destination rows: tap (a,b) of coarse pixel (y,x) -> (2y+a, 2x+b)
-            b_i = torch.arange(batch, device=dev).view(-1, 1, 1)
-            yy = torch.arange(h2, device=dev).view(1, -1, 1)
-            xx = torch.arange(w2, device=dev).view(1, 1, -1)
-            maps = []
-            for a in range(2):
-                for bb in range(2):
-                    maps.append(((b_i * h + 2 * yy + a) * w + 2 * xx + bb).reshape(-1))
-            t["up2"] = torch.stack(maps).to(torch.int32).contiguous()
-            self._bev_cache[key] = t
-        return self._bev_cache[key]
 
     def dense_pairs_ok(self, batch, h, w):
         """can this batch run its dense half on fp16-pair maps? Every 3 x 3 / stride 1 layer must take one of the window tiles the pair
@@ -615,7 +519,7 @@ class CenterPointEngine:
         layer are fp16-pair maps (ModelConfig.pair_rows_dense); the returned concat map is then a pair map, the head rows are fp32."""
         cfg = self.cfg
         pk = dict(in_pairs=True, out_pairs=True) if pairs else {}
-        T = self._bev_tables(batch, h, w)
+        T = bev_tables(self._bev_cache, batch, h, w, self.device)
         if getattr(self, "_rb_stage", None) != "backbone":     # called on its own (tests, tools): the input's range is unknown
             self._range_reset()
         self._rb_stage = None

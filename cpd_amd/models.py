@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import autograd_ops, iou3d_nms_utils, ops, train_ops
+from . import autograd_ops, iou3d_nms_utils, layer_table, ops, train_ops
 from . import spconv as _spconv_pkg
 from .spconv import pytorch as spconv
 from .spconv.pytorch import conv as _spc
@@ -375,7 +375,7 @@ class Conv2d(nn.Conv2d):
         k = self.kernel_size[0]
         ver = (self.weight._version, self.weight.data_ptr())
         if getattr(self, "_pk_ver", None) != ver:
-            self._pk = ops.pack_weight(self.weight.detach().permute(2, 3, 1, 0).reshape(k * k, self.in_channels, self.out_channels).contiguous())
+            self._pk = ops.pack_weight(layer_table.conv2d_kio(self.weight.detach()).contiguous())
             self._pk_ver = ver
         return self._pk
 
@@ -408,7 +408,7 @@ class Conv2d(nn.Conv2d):
         same = s == 1 and 2 * p == k - 1
         spec = autograd_ops.ConvSpec(nbr, k * k, b * ho * wo, dense=True, math=self.math,
                                      mode="same" if same else "strided", adjoint=adjoint, packed=self._pk)
-        w_kio = self.weight.permute(2, 3, 1, 0).reshape(k * k, c, self.out_channels)
+        w_kio = layer_table.conv2d_kio(self.weight)
         out = autograd_ops.gather_conv(_rows(x.float()), w_kio, self.bias, spec)
         return _nchw(out, b, ho, wo)
 
@@ -599,27 +599,18 @@ class SeparateHead(nn.Module):
         if cached is not None and cached[0] == key:
             return cached[1]
         names = list(self.sep_head_dict)
-        w1, s1, t1, slices = [], [], [], {}
         c = self.__getattr__(names[0])[0][0].in_channels
-        n_out = sum(self.__getattr__(n)[1].out_channels for n in names)
-        w2 = torch.zeros(9, c * len(names), n_out)
-        b2 = torch.zeros(n_out)
-        col = 0
+        kio = lambda conv: layer_table.conv2d_kio(conv.weight.detach().float().cpu())
         with torch.no_grad():
-            for hi, name in enumerate(names):
-                fc = self.__getattr__(name)
-                conv, bn, last = fc[0][0], fc[0][1], fc[1]
-                w1.append(conv.weight.detach().float().cpu().permute(2, 3, 1, 0).reshape(9, c, c))
-                sc, sh = _fold_batchnorm(bn, conv.bias)
-                s1.append(sc.cpu()); t1.append(sh.cpu())
-                co = last.out_channels
-                w2[:, hi * c:(hi + 1) * c, col:col + co] = last.weight.detach().float().cpu().permute(2, 3, 1, 0).reshape(9, c, co)
-                b2[col:col + co] = last.bias.detach().float().cpu()
-                slices[name] = (col, co)
-                col += co
-            img = dict(w1=ops.pack_weight(torch.cat(w1, dim=2).to(dev).contiguous()), s1=torch.cat(s1).to(dev), t1=torch.cat(t1).to(dev),
-                       w2=ops.pack_weight(w2.to(dev).contiguous()), b2=b2.to(dev), c=c, c1=c * len(names), n_out=n_out, slices=slices,
-                       ld=16 * ((n_out + 15) // 16))
+            fcs = [self.__getattr__(name) for name in names]
+            folds = [_fold_batchnorm(fc[0][1], fc[0][0].bias) for fc in fcs]
+            w1, s1, t1, w2, b2, slices = layer_table.fuse_branches(
+                [kio(fc[0][0]) for fc in fcs], [s.cpu() for s, _ in folds], [t.cpu() for _, t in folds],
+                [kio(fc[1]) for fc in fcs], [fc[1].bias.detach().float().cpu() for fc in fcs])
+            n_out = w2.shape[2]
+            img = dict(w1=ops.pack_weight(w1.to(dev).contiguous()), s1=s1.to(dev), t1=t1.to(dev),
+                       w2=ops.pack_weight(w2.to(dev).contiguous()), b2=b2.to(dev), c=c, c1=c * len(names), n_out=n_out,
+                       slices=dict(zip(names, slices)), ld=16 * ((n_out + 15) // 16))
         self._fused = (key, img)
         return img
 

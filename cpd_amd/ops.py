@@ -10,10 +10,6 @@ from . import _lib
 from ._lib import check, farr, iarr, lib, ptr, stream
 
 
-def _dev(t):
-    return t.device
-
-
 def _need_cuda(t, name):
     if not t.is_cuda:
         raise _lib.CpdHipError("%s must be a device (HIP) tensor" % name)

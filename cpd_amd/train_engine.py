@@ -18,12 +18,12 @@ There is no autograd graph: each layer object keeps what its backward needs from
 """
 import math
 import os
-from typing import Dict, List
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
-from . import _lib, center_loss, dist_utils, ops, train_ops
-from .engine import _DOWN, ModelConfig
+from . import _lib, center_loss, dist_utils, layer_table, ops, train_ops
+from .engine import _DOWN, ModelConfig, StridedStageChain, bev_tables
 
 
 class _Flat:
@@ -257,6 +257,16 @@ def one_cycle(step, total_steps, lr_max=3e-3, moms=(0.95, 0.85), div_factor=10.0
     return anneal(lr_max, low / 1e4, pct), anneal(moms[1], moms[0], pct)
 
 
+class _StageTables(NamedTuple):
+    """a strided stage's tables, as the trainer's forward and backward read them"""
+    nbr_dn: torch.Tensor
+    nbr_dn_t: torch.Tensor                 # the transposed rulebook (input gradient of the strided conv)
+    nbr_sub: Optional[torch.Tensor]
+    out_idx: torch.Tensor
+    out_shape: list
+    dense_rows: Optional[torch.Tensor]     # conv_out: HeightCompression's row map
+
+
 class CenterPointTrainer:
     """One data-parallel replica: `step(points_list, gt_boxes)` runs forward, loss, backward, the
     gradient all-reduce over `process_group` (RCCL) and the Adam update; returns the loss dict."""
@@ -334,119 +344,56 @@ class CenterPointTrainer:
         self._repack_all()
 
     # ------------------------------------------------------------------ graph
-    @staticmethod
-    def _bn(sd, name):
-        return {k: sd[name + "." + k] for k in ("weight", "bias", "running_mean", "running_var")}
-
-    @staticmethod
-    def _sparse_w(sd, name):
-        w = sd[name + ".weight"]                               # (Cout, kD, kH, kW, Cin)
-        return w.reshape(w.shape[0], -1, w.shape[-1]).permute(1, 2, 0)
-
-    @staticmethod
-    def _w2d(w):
-        return w.permute(2, 3, 1, 0).reshape(w.shape[2] * w.shape[3], w.shape[1], w.shape[0])
-
-    def _final_depth(self):
-        shape = self.cfg.sparse_shape
-        for stage in ["conv2", "conv3", "conv4", "conv_out"]:
-            k, s, pd = _DOWN[stage]
-            shape = ops.conv_out_shape(shape, k, s, pd)
-        return shape[0]
-
     def _build(self, sd):
+        """One _Conv per layer_table record, in the table's order: the flat store lays its slots out in creation order, [sparse | BEV |
+        head]. `_slots`: (record, its _Conv, its columns of that _Conv) in the table's order -- what _export walks back."""
         cfg, st = self.cfg, self.store
         self.layers: List[_Conv] = []
+        self.depth = layer_table.final_shape(cfg)[0]
+        bn_consts = {"sparse": self.SPARSE_BN, "bev": self.BEV_BN, "head": self.HEAD_BN}
+        all_columns = slice(None)
 
-        def mk(name, w_kio, bias, bn_name, bnp, relu=True, mode="same", up=1):
-            c = _Conv(st, name, w_kio, bias, self._bn(sd, bn_name) if bn_name else None, bnp[0], bnp[1], relu, mode, up)
+        def mk(name, w_kio, bias, bn, group, relu=True, mode="same", up=1):
+            eps, momentum = bn_consts[group] if bn else (0.0, 0.0)
+            c = _Conv(st, name, w_kio, bias, bn, eps, momentum, relu, mode, up)
             self.layers.append(c)
             return c
 
-        p = "backbone_3d."
-        S = {}
-        S["conv_input"] = mk(p + "conv_input.0", self._sparse_w(sd, p + "conv_input.0"), None, p + "conv_input.1",
-                             self.SPARSE_BN)
+        def params(L):
+            return (L.kio(sd[L.conv + ".weight"], cfg.out_features, self.depth), sd.get(L.conv + ".bias") if L.bias else None,
+                    {k: sd[L.bn + "." + k] for k in layer_table.BN_KEYS} if L.bn else None)
 
-        def block(name):
-            return (mk(name + ".conv1", self._sparse_w(sd, name + ".conv1"), sd.get(name + ".conv1.bias"), name + ".bn1",
-                       self.SPARSE_BN),
-                    mk(name + ".conv2", self._sparse_w(sd, name + ".conv2"), sd.get(name + ".conv2.bias"), name + ".bn2",
-                       self.SPARSE_BN))
-
-        S["conv1"] = [block(p + "conv1.0"), block(p + "conv1.1")]
-        for stage in ["conv2", "conv3", "conv4"]:
-            S[stage + ".down"] = mk(p + stage + ".0.0", self._sparse_w(sd, p + stage + ".0.0"), None, p + stage + ".0.1",
-                                    self.SPARSE_BN, mode="strided")
-            S[stage] = [block(p + stage + ".1"), block(p + stage + ".2")]
-        S["conv_out"] = mk(p + "conv_out.0", self._sparse_w(sd, p + "conv_out.0"), None, p + "conv_out.1", self.SPARSE_BN,
-                           mode="strided")
-        self.sparse = S
-        self._n_sparse_slots = len(st._pending)          # the flat store lays its slots out in creation order: [sparse | BEV | head]
-
-        p = "backbone_2d."
-        depth, C = self._final_depth(), cfg.out_features
-        self.depth = depth
-        self.bev_levels = []
-        for lvl in range(len(cfg.bev_layer_nums)):
-            convs = []
-            names = ["blocks.%d.1" % lvl] + ["blocks.%d.%d" % (lvl, 4 + 3 * k) for k in range(cfg.bev_layer_nums[lvl])]
-            bns = ["blocks.%d.2" % lvl] + ["blocks.%d.%d" % (lvl, 5 + 3 * k) for k in range(cfg.bev_layer_nums[lvl])]
-            for i, (cn, bnn) in enumerate(zip(names, bns)):
-                w = sd[p + cn + ".weight"]
-                if lvl == 0 and i == 0:     # reference channel c*D+z (height_compression.py:136-138) -> ours z*C+c
-                    w = w.reshape(w.shape[0], C, depth, 3, 3).permute(0, 2, 1, 3, 4).reshape(w.shape[0], depth * C, 3, 3)
-                mode = "strided" if (i == 0 and cfg.bev_layer_strides[lvl] != 1) else "same"
-                convs.append(mk(p + cn, self._w2d(w), None, p + bnn, self.BEV_BN, mode=mode))
-            u = cfg.bev_upsample_strides[lvl]
-            wd = sd[p + "deblocks.%d.0.weight" % lvl]                          # (Cin, Cout, u, u)
-            w_kio = wd.permute(0, 2, 3, 1).reshape(1, wd.shape[0], u * u * wd.shape[1])
-            de = mk(p + "deblocks.%d.0" % lvl, w_kio, None, p + "deblocks.%d.1" % lvl, self.BEV_BN, mode="up", up=u)
-            self.bev_levels.append((convs, de, u, wd.shape[1]))
-
-        p = "dense_head."
-        self.shared = mk(p + "shared_conv.0", self._w2d(sd[p + "shared_conv.0.weight"]), sd.get(p + "shared_conv.0.bias"),
-                         p + "shared_conv.1", self.HEAD_BN)
+        table = layer_table.centerpoint_layers(cfg)
+        at, first, last, where = {}, [], [], {}
+        for L in table:
+            if L.slot[0] == "head":
+                (last if L.slot[2] else first).append(L)
+                continue
+            at[L.slot] = mk(L.conv, *params(L), L.group, L.relu, L.mode, L.up)
+            where[L.slot] = (at[L.slot], all_columns)
+            if L.group == "sparse":
+                self._n_sparse_slots = len(st._pending)
+        self.sparse, self.bev_levels = layer_table.sparse_and_bev(cfg, at)
+        self.shared = at[("shared",)]
         # the five SeparateHead branches: first convs fused along Cout (BatchNorm is per channel, so
         # five BatchNorm2d(64) are one 320-channel one), second convs one small conv each
-        names = cfg.head_names()
         sc = cfg.shared_conv_channel
-        w1 = torch.cat([self._w2d(sd[p + "heads_list.0.%s.0.0.weight" % n]) for n in names], dim=2)
-        b1 = torch.cat([sd[p + "heads_list.0.%s.0.0.bias" % n] for n in names])
-        bn1 = {k: torch.cat([sd[p + "heads_list.0.%s.0.1.%s" % (n, k)] for n in names])
-               for k in ("weight", "bias", "running_mean", "running_var")}
-        self.head1 = _Conv(st, p + "heads.first", w1, b1, bn1, self.HEAD_BN[0], self.HEAD_BN[1], True)
-        self.layers.append(self.head1)
+        w1, b1, bn1 = zip(*[params(L) for L in first])
+        self.head1 = mk("dense_head.heads.first", torch.cat(w1, dim=2), torch.cat(b1),
+                        {k: torch.cat([bn[k] for bn in bn1]) for k in layer_table.BN_KEYS}, "head")
+        where.update((L.slot, (self.head1, slice(hi * sc, (hi + 1) * sc))) for hi, L in enumerate(first))
         self.head2 = []
         self.head_slices = {}
         col = 0
-        for hi, n in enumerate(names):
-            q = p + "heads_list.0.%s.1" % n
-            c = mk(q, self._w2d(sd[q + ".weight"]), sd[q + ".bias"], None, (0.0, 0.0), relu=False)
+        for hi, L in enumerate(last):
+            c = mk(L.conv, *params(L), L.group, L.relu)
+            where[L.slot] = (c, all_columns)
             self.head2.append((c, hi * sc, col))
-            self.head_slices[n] = (col, c.c_out)
+            self.head_slices[L.slot[1]] = (col, c.c_out)
             col += c.c_out
         self.n_head_out = col
         self.head_ld = 16 * ((col + 15) // 16)
-
-    # ------------------------------------------------------------------ tables
-    def _bev_tables(self, batch, h, w):
-        key = (batch, h, w)
-        if key not in self._bev_cache:
-            dev = self.device
-            t = {}
-            t["s1"] = ops.rulebook_conv2d(batch, h, w, 3, 3, 1, 1, dev)
-            t["s2"] = ops.rulebook_conv2d(batch, h, w, 3, 3, 2, 1, dev)
-            h2, w2 = t["s2"][1], t["s2"][2]
-            t["s2_t"] = train_ops.rulebook_conv2d_transpose(batch, h, w, 3, 3, 2, 1, dev)
-            t["s1_half"] = ops.rulebook_conv2d(batch, h2, w2, 3, 3, 1, 1, dev)
-            b_i = torch.arange(batch, device=dev).view(-1, 1, 1)
-            yy = torch.arange(h2, device=dev).view(1, -1, 1)
-            xx = torch.arange(w2, device=dev).view(1, 1, -1)
-            maps = [((b_i * h + 2 * yy + a) * w + 2 * xx + bb).reshape(-1) for a in range(2) for bb in range(2)]
-            t["up2"] = torch.stack(maps).to(torch.int32).contiguous()
-            self._bev_cache[key] = t
-        return self._bev_cache[key]
+        self._slots = [(L,) + where[L.slot] for L in table]
 
     # ------------------------------------------------------------------ forward / backward
     def _voxelize(self, points_list):
@@ -488,36 +435,14 @@ class CenterPointTrainer:
         shape = cfg.sparse_shape
         # The rulebooks depend on coordinates only, and their output-set sizes are the step's host read-backs. Round 5: the index chain of
         # the strided stages (output set, both rulebooks, the transposed one for the backward pass) runs on its own HIP stream, one
-        # stage ahead of the convolutions -- the read-backs wait for that stream only, so the conv chain is still queued without
-        # bubbles, and the 25 small index launches of a step overlap layers that do not fill the chip at one frame per GPU.
-        # (`index_side_stream=False`: the same order of calls on the main stream.) Tables are kept until the next step's
-        # chain starts, and that start waits for everything queued on the main stream (caching-allocator safety across streams).
-        stages = ["conv2", "conv3", "conv4", "conv_out"]
+        # stage ahead of the convolutions (engine.StridedStageChain) -- the read-backs wait for that stream only, so the conv chain is
+        # still queued without bubbles, and the 25 small index launches of a step overlap layers that do not fill the chip at one frame
+        # per GPU. (`index_side_stream=False`: the same order of calls on the main stream.)
         n0 = coords.shape[0]
-        side = None
-        self._index_keep = keep = []
 
-        def begin(stage, coords, shape):
+        def tables(stage, coords, index, shape, out_idx, out_index, out_shape):
+            """a stage's rulebooks; coords / index / shape = the stage's input level"""
             k, s, pd = _DOWN[stage]
-            return ops.conv_outset_begin(coords, batch, shape, k, s, pd)
-
-        if self.index_side_stream and coords.is_cuda:
-            side = _lib.side_stream(self.device, "index")
-            main = torch.cuda.current_stream(self.device)
-            side.wait_event(main.record_event())
-            with torch.cuda.stream(side):
-                pending = begin(stages[0], coords, shape)            # stage 2's output set is marked and counted beside the level-0 index build
-        index = ops.SiteIndex.build(coords, batch, shape)
-        ev_index = main.record_event() if side is not None else None
-
-        def stage_tables(stage, coords, index, shape, pending, after=None):
-            """a stage's output set (`pending`: its conv_outset_begin), the next stage's conv_outset_begin, its rulebooks; coords / index /
-            shape = the stage's input level; `after`: an event of the main stream that `index` is complete at"""
-            k, s, pd = _DOWN[stage]
-            out_idx, out_index, out_shape = ops.conv_outset_end(pending)
-            if after is not None:
-                torch.cuda.current_stream(self.device).wait_event(after)
-            nxt = begin(stages[stages.index(stage) + 1], out_idx, out_shape) if stage != "conv_out" else None
             nbr_dn = ops.rulebook_conv(out_idx, index, k, s, pd)
             nbr_dn_t = train_ops.rulebook_conv_transpose(coords, batch, shape, k, s, pd, out_index)
             nbr_sub = None if stage == "conv_out" else ops.rulebook_subm(out_idx, out_index)
@@ -525,52 +450,36 @@ class CenterPointTrainer:
             if stage == "conv_out":                          # HeightCompression's row map (used by the backward pass): coordinates only, too
                 (d, h, w), ci = out_shape, out_idx.long()
                 rows = ((ci[:, 0] * h + ci[:, 2]) * w + ci[:, 3]) * d + ci[:, 1]
-            return (stage, nbr_dn, nbr_dn_t, nbr_sub, out_idx.shape[0], out_idx, out_index, out_shape, rows, nxt)
+            return _StageTables(nbr_dn, nbr_dn_t, nbr_sub, out_idx, out_shape, rows)
 
-        def queue_tables(stage, coords, index, shape, pending, after=None):
-            if side is None:
-                return stage_tables(stage, coords, index, shape, pending), None
-            with torch.cuda.stream(side):
-                t = stage_tables(stage, coords, index, shape, pending, after)
-                return t, side.record_event()
-
+        chain = self._index_chain = StridedStageChain(tables, batch, self.device, self.index_side_stream and coords.is_cuda)
+        chain.start(coords, shape)                           # (stage 2's output set is marked and counted beside the level-0 index build)
+        index = ops.SiteIndex.build(coords, batch, shape)
+        chain.index_ready(index)
         nbr0 = ops.rulebook_subm(coords, index)
-        keep.append((coords, index, nbr0))
         tape = {"nbr0": nbr0, "stages": []}
         if getattr(self, "_repack_ev", None) is not None:      # the previous optimiser step's weight images (optimizer_step)
             torch.cuda.current_stream(self.device).wait_event(self._repack_ev)
             self._repack_ev = None
         x = S["conv_input"].forward(feats, nbr0, n0)
         x = self._blocks_fwd(S["conv1"], x, nbr0)
-        if side is None:
-            pending = begin(stages[0], coords, shape)
-        # a stage's chain is queued after the previous stage's layers (the count read-back inside can still block the host for a moment;
-        # the main stream has its work by then), its output set having been marked a stage earlier
-        nxt = queue_tables(stages[0], coords, index, shape, pending, after=ev_index)
-        for si, stage in enumerate(stages):
-            t, ev = nxt
-            keep.append(t)
-            if ev is not None:
-                main.wait_event(ev)
-            _, nbr_dn, nbr_dn_t, nbr_sub, n_stage = t[:5]
-            n_in = x.shape[0]
+        for stage in layer_table.STRIDED_STAGES:
+            t = chain.next()
+            n_in, n_stage = x.shape[0], t.out_idx.shape[0]
             if stage == "conv_out":
-                x = S["conv_out"].forward(x, nbr_dn, n_stage)
+                x = S["conv_out"].forward(x, t.nbr_dn, n_stage)
             else:
-                x = S[stage + ".down"].forward(x, nbr_dn, n_stage)
-                x = self._blocks_fwd(S[stage], x, nbr_sub)
-            tape["stages"].append((stage, nbr_sub, nbr_dn_t, n_in))
-            coords, index, shape = t[5], t[6], t[7]
-            if si + 1 < len(stages):
-                nxt = queue_tables(stages[si + 1], coords, index, shape, t[9])
-        dense_rows = t[8]
+                x = S[stage + ".down"].forward(x, t.nbr_dn, n_stage)
+                x = self._blocks_fwd(S[stage], x, t.nbr_sub)
+            tape["stages"].append((stage, t.nbr_sub, t.nbr_dn_t, n_in))
+        coords, shape, dense_rows = t.out_idx, t.out_shape, t.dense_rows
         d, h, w = shape
         C = x.shape[1]
         dense = ops.densify_nhwc(x, coords, batch, shape).view(batch * h * w, d * C)
         tape["dense_rows"] = dense_rows
         tape["dense_shape"] = (batch, h, w, d, C)
 
-        T = self._bev_tables(batch, h, w)
+        T = bev_tables(self._bev_cache, batch, h, w, self.device, transposed=True)
         n_full = batch * h * w
         c_cat = sum(cfg.bev_num_upsample_filters)
         cat = torch.empty((n_full, c_cat), dtype=torch.float32, device=self.device)
@@ -681,11 +590,7 @@ class CenterPointTrainer:
         side = self.store.side
         if side is None or not gt_boxes.is_cuda:
             return None
-        shape = self.cfg.sparse_shape
-        for stage in ["conv2", "conv3", "conv4", "conv_out"]:
-            k, s, pd = _DOWN[stage]
-            shape = ops.conv_out_shape(shape, k, s, pd)
-        hw = (shape[1], shape[2])
+        hw = tuple(layer_table.final_shape(self.cfg)[1:])
         main = torch.cuda.current_stream(self.device)
         gt_boxes.record_stream(side)
         with torch.cuda.stream(side):
@@ -795,67 +700,16 @@ class CenterPointTrainer:
         return self._export(self.store.g, False)
 
     def _export(self, V, with_stats):
-        cfg = self.cfg
         sd = {}
-
-        def bn_out(c, name, sl=slice(None)):
-            sd[name + ".weight"] = V(c.gn)[sl].clone()
-            sd[name + ".bias"] = V(c.be)[sl].clone()
-            if with_stats:
-                sd[name + ".running_mean"] = c.running_mean[sl].clone()
-                sd[name + ".running_var"] = c.running_var[sl].clone()
-                sd[name + ".num_batches_tracked"] = torch.tensor(self.steps_done, dtype=torch.long)
-
-        def sparse_out(c, name, k):
-            w = V(c.wn)                                      # [kv, ci, co]
-            sd[name + ".weight"] = w.permute(2, 0, 1).reshape(c.c_out, k[0], k[1], k[2], c.c_in).clone()
+        for L, c, cols in self._slots:
+            sd[L.conv + ".weight"] = L.from_kio(V(c.wn)[:, :, cols], self.cfg.out_features, self.depth).clone()
             if c.bn_:
-                sd[name + ".bias"] = V(c.bn_).clone()
-
-        def conv2d_out(c, name, k=3):
-            w = V(c.wn)                                      # [k*k, ci, co]
-            sd[name + ".weight"] = w.view(k, k, c.c_in, c.c_out).permute(3, 2, 0, 1).clone()
-            if c.bn_:
-                sd[name + ".bias"] = V(c.bn_).clone()
-
-        p = "backbone_3d."
-        S = self.sparse
-        sparse_out(S["conv_input"], p + "conv_input.0", [3, 3, 3]); bn_out(S["conv_input"], p + "conv_input.1")
-
-        def block_out(blk, name):
-            for c, cn, bn in ((blk[0], ".conv1", ".bn1"), (blk[1], ".conv2", ".bn2")):
-                sparse_out(c, name + cn, [3, 3, 3]); bn_out(c, name + bn)
-
-        block_out(S["conv1"][0], p + "conv1.0"); block_out(S["conv1"][1], p + "conv1.1")
-        for stage in ["conv2", "conv3", "conv4"]:
-            sparse_out(S[stage + ".down"], p + stage + ".0.0", _DOWN[stage][0]); bn_out(S[stage + ".down"], p + stage + ".0.1")
-            block_out(S[stage][0], p + stage + ".1"); block_out(S[stage][1], p + stage + ".2")
-        sparse_out(S["conv_out"], p + "conv_out.0", _DOWN["conv_out"][0]); bn_out(S["conv_out"], p + "conv_out.1")
-
-        p = "backbone_2d."
-        depth, C = self.depth, cfg.out_features
-        for lvl, (convs, de, u, c_up) in enumerate(self.bev_levels):
-            names = ["blocks.%d.1" % lvl] + ["blocks.%d.%d" % (lvl, 4 + 3 * k) for k in range(cfg.bev_layer_nums[lvl])]
-            bns = ["blocks.%d.2" % lvl] + ["blocks.%d.%d" % (lvl, 5 + 3 * k) for k in range(cfg.bev_layer_nums[lvl])]
-            for i, (c, cn, bnn) in enumerate(zip(convs, names, bns)):
-                conv2d_out(c, p + cn)
-                if lvl == 0 and i == 0:
-                    w = sd[p + cn + ".weight"]
-                    sd[p + cn + ".weight"] = w.reshape(w.shape[0], depth, C, 3, 3).permute(0, 2, 1, 3, 4).reshape(
-                        w.shape[0], depth * C, 3, 3).clone()
-                bn_out(c, p + bnn)
-            w = V(de.wn)                                     # [1, ci, u*u*co]
-            sd[p + "deblocks.%d.0.weight" % lvl] = w.view(de.c_in, u, u, c_up).permute(0, 3, 1, 2).clone()
-            bn_out(de, p + "deblocks.%d.1" % lvl)
-        p = "dense_head."
-        conv2d_out(self.shared, p + "shared_conv.0"); bn_out(self.shared, p + "shared_conv.1")
-        sc = cfg.shared_conv_channel
-        w1 = V(self.head1.wn)
-        for hi, n in enumerate(cfg.head_names()):
-            q = p + "heads_list.0.%s." % n
-            sl = slice(hi * sc, (hi + 1) * sc)
-            sd[q + "0.0.weight"] = w1[:, :, sl].reshape(3, 3, sc, sc).permute(3, 2, 0, 1).clone()
-            sd[q + "0.0.bias"] = V(self.head1.bn_)[sl].clone()
-            bn_out(self.head1, q + "0.1", sl)
-            conv2d_out(self.head2[hi][0], q + "1")
+                sd[L.conv + ".bias"] = V(c.bn_)[cols].clone()
+            if L.bn:
+                sd[L.bn + ".weight"] = V(c.gn)[cols].clone()
+                sd[L.bn + ".bias"] = V(c.be)[cols].clone()
+                if with_stats:
+                    sd[L.bn + ".running_mean"] = c.running_mean[cols].clone()
+                    sd[L.bn + ".running_var"] = c.running_var[cols].clone()
+                    sd[L.bn + ".num_batches_tracked"] = torch.tensor(self.steps_done, dtype=torch.long)
         return sd
