@@ -157,6 +157,9 @@ SIGNATURES = {
     "cpd_outline_dbscan": (_I, [_VP, _VP, _VP, _I, _I, _D, _I, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_outline_boxes_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_outline_boxes": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, ctypes.POINTER(_D), _I, _VP, _VP, _SZ, _VP]),
+    "cpd_ppscore_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cpd_ppscore": (_I, [_VP, _I, _I, _I, _VP, _I3, _I, _I, _I, ctypes.POINTER(_D), ctypes.POINTER(_D), _D, _VP, _VP, _VP, _SZ,
+                         _VP]),
 }
 
 

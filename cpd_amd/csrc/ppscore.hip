@@ -1,0 +1,287 @@
+// ppscore.hip -- CPD's PP-score precompute (cpd/unsupervised_core/precompute_ppscore.py) for ONE current frame against its
+// T <= 16 traversals per call:
+//   a. every traversal point goes sweep -> world (its own pose) -> current frame (inverse of the current pose): two float64
+//      products in the accumulation order of the reference's np.mat product (pp_row below), each rounded to float32 (the
+//      rounding in world coordinates is the reference's and is kept);
+//   b. one hashed uniform grid of side r over all traversals, key (traversal, cx, cy, cz) with floor((double)coord / r) cell
+//      coordinates taken modulo 2^18: count per slot, prefix, fill float4 members in cell order (as outline.hip's DBSCAN grid);
+//   c. one lane per (query point, traversal) walks the 27 cells and counts the members with float64
+//      (dx*dx + dy*dy) + dz*dz <= r*r (cKDTree.query_ball_point(..., return_length=True): inclusive); lanes of a wave are
+//      consecutive query rows of one traversal, which in scan order walk the same cells. Queries are the RAW rows of the
+//      current frame, not transformed (that is what the reference does);
+//   d. compute_ephe_score: P = c / (sum c + 1e-8), H = sum -P log(P + 1e-8) / log(T) in float64, stored as float16 bits;
+//      T < 2 gives NaN (the reference divides by log(1) = 0).
+// Integer atomics only (slot claims, counts, cursors): the order of a cell's members varies from call to call, the counts
+// do not. Built with -ffp-contract=off: the compiler fuses nothing; the only fused multiply-adds are the explicit ones of
+// the pose product, which are the reference's.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int PP_MAX_TRAV = 16;
+constexpr unsigned long long PP_EMPTY = ~0ull;
+
+struct PpArgs {
+    const void *query, *ref;
+    int n_query, query_stride, query_half;
+    int n_ref, ref_stride, ref_half;
+    int n_trav, has_pose;
+    int32_t off[PP_MAX_TRAV + 1];
+    double pose[PP_MAX_TRAV][12];   // rows 0..2 of the 4x4 sweep -> world matrices
+    double cur_inv[12];             // rows 0..2 of inverse(current pose)
+    double r, r2, log_t;
+    unsigned long long hmask;
+    unsigned long long *keys;       // [H]
+    int32_t *ccount;                // [H]
+    int2 *range;                    // [H] (first member, cursor); the cursor is the end of the cell once the fill has run
+    int32_t *cell;                  // [n_ref] slot
+    float4 *members;                // [n_ref] (x, y, z, 0) in cell order
+    int32_t *counts;                // [n_query][n_trav]
+    uint16_t *h;                    // [n_query] float16 bits
+};
+
+__device__ __forceinline__ void pp_load(const void *base, int is_half, int stride, int i, float &x, float &y, float &z) {
+    if (is_half) {
+        const _Float16 *p = static_cast<const _Float16 *>(base) + (size_t)i * stride;
+        x = (float)p[0], y = (float)p[1], z = (float)p[2];
+    } else {
+        const float *p = static_cast<const float *>(base) + (size_t)i * stride;
+        x = p[0], y = p[1], z = p[2];
+    }
+}
+
+// One points_rigid_transform product (l.36-45): the np.mat product is a dgemm whose inner loop accumulates over k with fused
+// multiply-adds, acc = m0*x; acc = fma(m1, y, acc); acc = fma(m2, z, acc); acc + m3 (the last step multiplies by the exact 1
+// of the homogeneous column). The unfused (m0*x + m1*y) + m2*z + m3 of roi_pool.hip's rigid3 differs from it by one float64
+// ulp on some rows, which survives the rounding to float32 where the sum cancels to almost zero (DESIGN 5m has the counts).
+// These are explicit fma() calls; the file is still built with -ffp-contract=off, so nothing else is ever fused.
+__device__ __forceinline__ float pp_row(const double *m, double x, double y, double z) {
+    return (float)__dadd_rn(__fma_rn(m[2], z, __fma_rn(m[1], y, __dmul_rn(m[0], x))), m[3]);
+}
+__device__ __forceinline__ void pp_rigid3(const double *m, float x, float y, float z, float &ox, float &oy, float &oz) {
+    const double dx = x, dy = y, dz = z;
+    ox = pp_row(m, dx, dy, dz);
+    oy = pp_row(m + 4, dx, dy, dz);
+    oz = pp_row(m + 8, dx, dy, dz);
+}
+
+// traversal point i in the current frame's coordinates, and its traversal
+__device__ __forceinline__ int pp_ref_point(const PpArgs &a, int i, float &x, float &y, float &z) {
+    int t = 0;
+    while (t + 1 < a.n_trav && i >= a.off[t + 1]) ++t;
+    pp_load(a.ref, a.ref_half, a.ref_stride, i, x, y, z);
+    if (a.has_pose) {
+        float wx, wy, wz;
+        pp_rigid3(a.pose[t], x, y, z, wx, wy, wz);
+        pp_rigid3(a.cur_inv, wx, wy, wz, x, y, z);
+    }
+    return t;
+}
+
+__device__ __forceinline__ void pp_cell(const PpArgs &a, float x, float y, float z, long long c[3]) {
+    c[0] = (long long)floor((double)x / a.r);
+    c[1] = (long long)floor((double)y / a.r);
+    c[2] = (long long)floor((double)z / a.r);
+}
+// cells that alias modulo 2^18 share a slot: that costs distance tests, never a wrong count (every candidate is decided by
+// its distance, and the 27 keys of one query stay distinct). t <= 15, so no key equals PP_EMPTY.
+__device__ __forceinline__ unsigned long long pp_key(int t, long long cx, long long cy, long long cz) {
+    const unsigned long long m = (1ull << 18) - 1;
+    return ((unsigned long long)t << 54) | (((unsigned long long)cx & m) << 36) | (((unsigned long long)cy & m) << 18) |
+           ((unsigned long long)cz & m);
+}
+__device__ __forceinline__ unsigned long long pp_hash(unsigned long long k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+__global__ void __launch_bounds__(256) pp_insert_kernel(PpArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_ref) return;
+    float x, y, z;
+    const int t = pp_ref_point(a, i, x, y, z);
+    long long c[3];
+    pp_cell(a, x, y, z, c);
+    const unsigned long long key = pp_key(t, c[0], c[1], c[2]);
+    unsigned long long s = pp_hash(key) & a.hmask;
+    for (;;) {   // the table holds >= 2 slots per point: a free slot always exists
+        const unsigned long long prev = atomicCAS(a.keys + s, PP_EMPTY, key);
+        if (prev == PP_EMPTY || prev == key) break;
+        s = (s + 1) & a.hmask;
+    }
+    a.cell[i] = (int)s;
+    atomicAdd(a.ccount + s, 1);
+}
+
+__global__ void __launch_bounds__(256) pp_fill_kernel(PpArgs a) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_ref) return;
+    float x, y, z;
+    pp_ref_point(a, i, x, y, z);
+    const int pos = atomicAdd(&a.range[a.cell[i]].y, 1);
+    a.members[pos] = make_float4(x, y, z, 0.f);
+}
+
+__global__ void __launch_bounds__(256) pp_count_kernel(PpArgs a) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = blockIdx.y;
+    if (q >= a.n_query) return;
+    int n = 0;
+    if (a.off[t + 1] > a.off[t]) {
+        float fx, fy, fz;
+        pp_load(a.query, a.query_half, a.query_stride, q, fx, fy, fz);
+        const double x = fx, y = fy, z = fz;
+        long long c[3];
+        pp_cell(a, fx, fy, fz, c);
+        for (int dx = -1; dx <= 1; ++dx)
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dz = -1; dz <= 1; ++dz) {
+                    const unsigned long long key = pp_key(t, c[0] + dx, c[1] + dy, c[2] + dz);
+                    unsigned long long s = pp_hash(key) & a.hmask;
+                    unsigned long long k;
+                    while ((k = a.keys[s]) != key && k != PP_EMPTY) s = (s + 1) & a.hmask;
+                    if (k != key) continue;
+                    const int2 rg = a.range[s];
+                    for (int m = rg.x; m < rg.y; ++m) {
+                        const float4 p = a.members[m];
+                        const double ex = x - (double)p.x, ey = y - (double)p.y, ez = z - (double)p.z;
+                        n += ((ex * ex + ey * ey) + ez * ez <= a.r2) ? 1 : 0;
+                    }
+                }
+    }
+    a.counts[(size_t)q * a.n_trav + t] = n;
+}
+
+// float64 -> float16 with ONE rounding (numpy's astype(np.float16)): the float32 step rounds to odd, which keeps the sticky
+// information the final round-to-nearest-even needs (float32 carries more than two bits beyond float16's precision)
+__device__ __forceinline__ uint16_t pp_half_bits(double d) {
+    float f = (float)d;
+    if ((double)f != d) {
+        uint32_t u = __float_as_uint(f);
+        if (fabs((double)f) > fabs(d)) u -= 1;   // back towards zero (f != 0 here)
+        f = __uint_as_float(u | 1u);
+    }
+    const _Float16 hf = (_Float16)f;
+    uint16_t b;
+    __builtin_memcpy(&b, &hf, 2);
+    return b;
+}
+
+// compute_ephe_score (precompute_ppscore.py:16-21); the sum over traversals runs in traversal order
+__global__ void __launch_bounds__(256) pp_score_kernel(PpArgs a) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.n_query) return;
+    if (a.n_trav < 2) {
+        a.h[q] = 0x7e00;
+        return;
+    }
+    const int32_t *c = a.counts + (size_t)q * a.n_trav;
+    long long total = 0;
+    for (int t = 0; t < a.n_trav; ++t) total += c[t];
+    const double den = (double)total + 1e-8;
+    double hsum = 0.0;
+    for (int t = 0; t < a.n_trav; ++t) {
+        const double p = (double)c[t] / den;
+        const double term = (-p) * log(p + 1e-8);
+        hsum = t == 0 ? term : hsum + term;
+    }
+    a.h[q] = pp_half_bits(hsum / a.log_t);
+}
+
+struct PpLayout {
+    size_t keys, ccount, range, cell, members, counts, scan, total;
+    unsigned long long hsize;
+};
+PpLayout pp_layout(long long n_query, long long n_ref, int n_trav) {
+    PpLayout L;
+    unsigned long long h = 1024;
+    while (h < 2ull * (unsigned long long)n_ref) h <<= 1;
+    L.hsize = h;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o += cpd_align(bytes);
+        return at;
+    };
+    L.keys = take(h * 8);
+    L.ccount = take(h * 4);
+    L.range = take(h * 8);
+    L.cell = take((size_t)n_ref * 4);
+    L.members = take((size_t)n_ref * 16);
+    L.counts = take((size_t)n_query * (size_t)(n_trav > 0 ? n_trav : 1) * 4);
+    L.scan = take((size_t)scan_num_blocks((long long)h) * 4);
+    L.total = o;
+    return L;
+}
+
+template <class T>
+T *at(void *ws, size_t off) {
+    return reinterpret_cast<T *>(static_cast<char *>(ws) + off);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t cpd_ppscore_workspace_bytes(int n_query, int n_ref_total, int n_trav) {
+    if (n_query < 0 || n_ref_total < 0 || n_trav < 0 || n_trav > PP_MAX_TRAV) return 0;
+    return pp_layout(n_query, n_ref_total, n_trav).total;
+}
+
+int cpd_ppscore(const void *query, int n_query, int query_stride, int query_dtype, const void *ref, const int32_t *trav_offsets,
+                int n_trav, int ref_stride, int ref_dtype, const double *poses, const double *cur_pose_inv, double radius,
+                int32_t *counts, uint16_t *h, void *workspace, size_t workspace_bytes, cpd_stream_t stream) {
+    if (n_trav > PP_MAX_TRAV) return CPD_ERR_UNSUPPORTED;
+    if (n_query < 0 || n_trav < 0 || !trav_offsets || !(radius > 0.0) || !(radius * radius < INFINITY)) return CPD_ERR_ARG;
+    if ((query_dtype != 0 && query_dtype != 1) || (ref_dtype != 0 && ref_dtype != 1)) return CPD_ERR_ARG;
+    if (query_stride < 3 || ref_stride < 3 || (poses == nullptr) != (cur_pose_inv == nullptr)) return CPD_ERR_ARG;
+    if (trav_offsets[0] != 0) return CPD_ERR_ARG;
+    for (int t = 0; t < n_trav; ++t)
+        if (trav_offsets[t + 1] < trav_offsets[t]) return CPD_ERR_ARG;
+    const int n_ref = trav_offsets[n_trav];
+    if ((n_query > 0 && !query) || (n_ref > 0 && !ref)) return CPD_ERR_ARG;
+    const PpLayout L = pp_layout(n_query, n_ref, n_trav);
+    if (!workspace || workspace_bytes < L.total) return CPD_ERR_WORKSPACE;
+    hipStream_t st = cpd_s(stream);
+    PpArgs a;
+    a.query = query, a.ref = ref, a.n_query = n_query, a.query_stride = query_stride, a.query_half = query_dtype;
+    a.n_ref = n_ref, a.ref_stride = ref_stride, a.ref_half = ref_dtype, a.n_trav = n_trav, a.has_pose = poses != nullptr;
+    for (int t = 0; t <= PP_MAX_TRAV; ++t) a.off[t] = trav_offsets[t < n_trav ? t : n_trav];
+    for (int t = 0; t < PP_MAX_TRAV; ++t)
+        for (int k = 0; k < 12; ++k) a.pose[t][k] = (poses && t < n_trav) ? poses[(size_t)t * 16 + k] : 0.0;
+    for (int k = 0; k < 12; ++k) a.cur_inv[k] = cur_pose_inv ? cur_pose_inv[k] : 0.0;
+    a.r = radius, a.r2 = radius * radius, a.log_t = log((double)(n_trav > 0 ? n_trav : 1)), a.hmask = L.hsize - 1;
+    a.keys = at<unsigned long long>(workspace, L.keys), a.ccount = at<int32_t>(workspace, L.ccount);
+    a.range = at<int2>(workspace, L.range), a.cell = at<int32_t>(workspace, L.cell);
+    a.members = at<float4>(workspace, L.members);
+    a.counts = counts ? counts : at<int32_t>(workspace, L.counts);
+    a.h = h;
+    if (n_query == 0 || (n_trav == 0 && !h)) return CPD_OK;
+    if (n_trav > 0) {
+        CPD_HIP_TRY(hipMemsetAsync(a.keys, 0xff, L.hsize * 8, st));
+        if (n_ref > 0) {
+            CPD_HIP_TRY(hipMemsetAsync(a.ccount, 0, L.hsize * 4, st));
+            const unsigned blocks = (unsigned)cpd_div_up(n_ref, 256);
+            pp_insert_kernel<<<blocks, 256, 0, st>>>(a);
+            int2 *range = a.range;
+            const int32_t *ccount = a.ccount;
+            const int rc = device_scan(
+                (long long)L.hsize, [=] __device__(long long i) { return (uint32_t)ccount[i]; },
+                [=] __device__(long long i, uint32_t, uint32_t pre) { range[i] = make_int2((int)pre, (int)pre); },
+                at<uint32_t>(workspace, L.scan), nullptr, -1, st);
+            if (rc != CPD_OK) return rc;
+            pp_fill_kernel<<<blocks, 256, 0, st>>>(a);
+        }
+        pp_count_kernel<<<dim3((unsigned)cpd_div_up(n_query, 256), (unsigned)n_trav), 256, 0, st>>>(a);
+    }
+    if (h) pp_score_kernel<<<(unsigned)cpd_div_up(n_query, 256), 256, 0, st>>>(a);
+    return cpd_check_launch();
+}
+
+}  // extern "C"

@@ -366,3 +366,67 @@ def _settle_segments(pts, dtype, ulps=2):
         raise RuntimeError("outline_scene: could not settle segment indices")
     _settle_segments.last_moved = moved
     return pts
+
+
+# ---- PP-score sequence (cpd_amd.ppscore) ---------------------------------------------------------------------------------
+
+def ppscore_sequence(seed, n_frames, n_az, dtype=np.float16, origin=(0.0, 0.0, 0.0), n_parked=12, n_moving=10, frame_step=1):
+    """A short drive for the PP-score precompute (cpd_amd.ppscore): `n_frames` sweeps of the waymo_cloud beam pattern (64
+    beams x n_az azimuths, sensor 2 m above z = 0, 75 m range, 2 cm range noise), each ray-cast from an ego pose that moves
+    0.35 m and yaws 0.4 deg per frame, against
+      * a static world: flat ground, the waymo_cloud ring of 12 buildings, `n_parked` parked vehicle-size boxes;
+      * `n_moving` boxes at constant velocity (0.3..1.2 m per frame along their heading), which leave points where the other
+        traversals see nothing.
+    Returns (frames, poses): frames[k] is [N_k, 5] of `dtype` (x, y, z, intensity, elongation in the vehicle frame, as Waymo
+    frames are saved), poses[k] the float64 4x4 vehicle -> world matrix with `origin` added to its translation (Waymo
+    translations are thousands of metres: that is where the float32 rounding in world coordinates shows). frame_step = 5
+    returns every fifth sweep of the drive (the traversals of the default window) without casting the ones between."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.float16, np.float32):
+        raise TypeError("ppscore_sequence: float16 or float32")
+    rng = np.random.default_rng(seed + 9000)
+    sensor_z = 2.0
+    elev = np.deg2rad(np.linspace(-17.6, 2.4, 64))
+    az = np.linspace(0.0, 2 * np.pi, n_az, endpoint=False)
+    e, a = np.meshgrid(elev, az, indexing="ij")
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], -1).reshape(-1, 3)
+    dz = d[:, 2]
+    t_ground = np.where(dz < -1e-6, -sensor_z / np.minimum(dz, -1e-6), np.inf)
+    static, moving = [], []
+    for k in range(12):
+        ang = 2 * np.pi * k / 12
+        size = (rng.uniform(8, 14), rng.uniform(8, 14), rng.uniform(6, 14))
+        static.append((np.array([62 * np.cos(ang), 62 * np.sin(ang), size[2] / 2]), size, ang))
+    for _ in range(n_parked):
+        r, ang = rng.uniform(6, 40), rng.uniform(0, 2 * np.pi)
+        size = (rng.uniform(3.6, 5.2), rng.uniform(1.7, 2.2), rng.uniform(1.4, 2.1))
+        static.append((np.array([r * np.cos(ang), r * np.sin(ang), size[2] / 2]), size, rng.uniform(-np.pi, np.pi)))
+    for _ in range(n_moving):
+        r, ang = rng.uniform(6, 30), rng.uniform(0, 2 * np.pi)
+        size = (rng.uniform(3.6, 5.2), rng.uniform(1.7, 2.2), rng.uniform(1.4, 2.1))
+        yaw, speed = rng.uniform(-np.pi, np.pi), rng.uniform(0.3, 1.2)
+        moving.append((np.array([r * np.cos(ang), r * np.sin(ang), size[2] / 2]), size, yaw,
+                       speed * np.array([np.cos(yaw), np.sin(yaw), 0.0])))
+    frames, poses = [], []
+    for k in range(0, n_frames * frame_step, frame_step):
+        yaw_k = np.deg2rad(0.4) * k
+        ego = np.array([0.35 * k, 0.05 * np.sin(0.5 * k), 0.0])
+        cs, sn = np.cos(yaw_k), np.sin(yaw_k)
+        rot = np.array([[cs, -sn, 0.0], [sn, cs, 0.0], [0.0, 0.0, 1.0]])
+        t_best = t_ground.copy()
+        for c, size, yaw in static + [(c0 + k * v, size, yaw) for c0, size, yaw, v in moving]:
+            t_best = np.minimum(t_best, _ray_obb(d, sensor_z, rot.T @ (c - ego), size, yaw - yaw_k))
+        hit = np.isfinite(t_best) & (t_best < 75.0)
+        t = t_best[hit] + rng.normal(0, 0.02, hit.sum())
+        pts = d[hit] * t[:, None]
+        pts[:, 2] += sensor_z
+        out = np.empty((pts.shape[0], 5), dtype)
+        out[:, :3] = pts
+        out[:, 3] = rng.uniform(0, 1, pts.shape[0])
+        out[:, 4] = rng.uniform(0, 1, pts.shape[0])
+        pose = np.eye(4)
+        pose[:3, :3] = rot
+        pose[:3, 3] = ego + np.asarray(origin, np.float64)
+        frames.append(out)
+        poses.append(pose)
+    return frames, poses

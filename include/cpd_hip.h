@@ -858,6 +858,25 @@ int cpd_outline_boxes(const float *xyz, const int32_t *frame_off, const int32_t 
                       const int32_t *labels, const int32_t *n_clusters, int apply_cluster_filter, const double params[8],
                       int box_cap, double *out, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
 
+/* ---- PP-score precompute (csrc/ppscore.hip): cpd/unsupervised_core/precompute_ppscore.py for ONE current frame against its
+ * n_trav <= 16 traversals. Caller-owned workspace; no allocation, no read-back, no host synchronisation inside a call. */
+size_t cpd_ppscore_workspace_bytes(int n_query, int n_ref_total, int n_trav);
+/* compute_ppscore (l.23-34: one cKDTree per traversal, count_neighbors l.8-14, compute_ephe_score l.16-21) with the two
+ * points_rigid_transform products of save_pp_score (l.36-45, 85-94) folded in. query [n_query][query_stride] and ref
+ * [n_ref_total][ref_stride] are DEVICE rows of float32 (dtype 0) or float16 (dtype 1), x y z in the first three columns;
+ * traversal t is rows trav_offsets[t] .. trav_offsets[t + 1] of ref (HOST int32 [n_trav + 1], trav_offsets[0] = 0). poses (HOST
+ * [n_trav][16] row-major sweep -> world) and cur_pose_inv (HOST [16], inverse of the current pose) are given together or both
+ * NULL (ref is already in the current frame): each product is the float64 accumulation of the reference's np.mat product
+ * (m0*x, then fused multiply-adds of m1*y and m2*z, then + m3) rounded to float32. The query
+ * rows are used as they are (the reference does not transform them). counts [n_query][n_trav] (DEVICE, may be NULL): points
+ * of traversal t with float64 (dx*dx + dy*dy) + dz*dz <= radius*radius, inclusive. h [n_query] (DEVICE, may be NULL): the
+ * normalised entropy H = sum_t -P log(P + 1e-8) / log(n_trav), P = c / (sum c + 1e-8), as float16 bits; NaN (0x7e00) where
+ * n_trav < 2 (the reference divides by log(1) = 0). An empty traversal gives a zero column; n_query = 0 is legal.
+ * CPD_ERR_UNSUPPORTED: n_trav > 16; CPD_ERR_ARG: radius <= 0 or NaN, bad offsets / strides / dtypes. */
+int cpd_ppscore(const void *query, int n_query, int query_stride, int query_dtype, const void *ref, const int32_t *trav_offsets,
+                int n_trav, int ref_stride, int ref_dtype, const double *poses, const double *cur_pose_inv, double radius,
+                int32_t *counts, uint16_t *h, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
