@@ -160,6 +160,14 @@ SIGNATURES = {
     "cpd_ppscore_workspace_bytes": (_SZ, [_I, _I, _I]),
     "cpd_ppscore": (_I, [_VP, _I, _I, _I, _VP, _I3, _I, _I, _I, ctypes.POINTER(_D), ctypes.POINTER(_D), _D, _VP, _VP, _VP, _SZ,
                          _VP]),
+    "cpd_cproto_crop_workspace_bytes": (_SZ, [_I]),
+    "cpd_cproto_crop_count": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _VP, _SZ, _VP]),
+    "cpd_cproto_crop_fill": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP]),
+    "cpd_cproto_filter_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_cproto_filter": (_I, [_VP, _I, _VP, _VP, _VP, _I, _I, _D, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_cproto_score_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_cproto_score": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I3, _I, _I, _I, _D, _VP, _VP, _VP, _VP,
+                              _VP, _VP, _VP, _SZ, _VP]),
 }
 
 

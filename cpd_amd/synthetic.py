@@ -308,6 +308,8 @@ def outline_scene(seed=0, dtype=np.float16, n_az=2650, n_vehicles=14, n_pedestri
         ang = 2 * np.pi * k / 12
         size = (rng.uniform(8, 14), rng.uniform(8, 14), rng.uniform(6, 14))
         objs.append((np.array([62 * np.cos(ang), 62 * np.sin(ang), size[2] / 2]), size, ang))
+    names = ['Vehicle'] * n_vehicles + ['Pedestrian'] * n_pedestrians + ['Cyclist'] * n_cyclists + ['Dis_Small'] * n_clutter
+    outline_scene.last_objects = [(c, size, yaw, name) for (c, size, yaw), name in zip(objs, names)]   # for cproto_sequence
     for c, size, yaw in objs:
         t = _ray_obb(d, sensor_z, c, size, yaw)
         closer = t < t_best
@@ -430,3 +432,38 @@ def ppscore_sequence(seed, n_frames, n_az, dtype=np.float16, origin=(0.0, 0.0, 0
         frames.append(out)
         poses.append(pose)
     return frames, poses
+
+
+# ---- C_PROTO refiner input (cpd_amd.cproto) --------------------------------------------------------------------------------
+
+def cproto_sequence(seed, n_az=1100, dtypes=(np.float16, np.float32, np.float16)):
+    """A short sequence for the C_PROTO refiner's first stage (cpd_amd.cproto): len(dtypes) outline_scene sweeps with poses
+    and the info list an initial label generator would have left (`outline_box` [K, 7] float64, `outline_cls`, `outline_ids`,
+    `pose`), the boxes being the scene's objects with jittered centre (N(0, 0.12 m)), size (x 0.92..1.15) and heading
+    (N(0, 0.04 rad)), plus the low clutter as 'Dis_Small', which the refiner skips.
+      * even frames are the sweep of scene `seed` from one pose, so an object keeps its track id and its place: ids recur
+        and their prototypes are static;
+      * odd frames are scene `seed + 1` from a pose 6 m on, with ids of their own -- except that its even-numbered vehicles
+        take the ids of scene `seed`'s, whose global position therefore jumps by metres: the moving tracks.
+    Returns (frames, infos): frames[k] is [N_k, 5] of dtypes[k]."""
+    rng = np.random.default_rng(seed + 11000)
+    frames, infos = [], []
+    for k, dt in enumerate(dtypes):
+        odd = k % 2
+        pts = outline_scene(seed + odd, np.dtype(dt), n_az=n_az)
+        objs = outline_scene.last_objects
+        yaw_k = np.deg2rad(3.0) * odd
+        pose = np.eye(4)
+        pose[:3, :3] = [[np.cos(yaw_k), -np.sin(yaw_k), 0.0], [np.sin(yaw_k), np.cos(yaw_k), 0.0], [0.0, 0.0, 1.0]]
+        pose[:3, 3] = [1200.0 + 6.0 * odd, -340.0 + 0.5 * odd, 12.0]
+        boxes, cls, ids = [], [], []
+        for j, (c, size, yaw, name) in enumerate(objs):
+            sz = np.asarray(size) * rng.uniform(0.92, 1.15, 3)
+            ctr = np.array([c[0], c[1], sz[2] / 2]) + np.append(rng.normal(0, 0.12, 2), 0.0)
+            boxes.append([ctr[0], ctr[1], ctr[2], sz[0], sz[1], sz[2], yaw + rng.normal(0, 0.04)])
+            cls.append(name)
+            ids.append(10 + j if name == 'Vehicle' and j % 2 == 0 else 100 * odd + 10 + j)
+        frames.append(pts)
+        infos.append(dict(outline_box=np.array(boxes, np.float64), outline_cls=np.array(cls), outline_ids=np.array(ids),
+                          pose=pose))
+    return frames, infos

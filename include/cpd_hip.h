@@ -877,6 +877,56 @@ int cpd_ppscore(const void *query, int n_query, int query_stride, int query_dtyp
                 int n_trav, int ref_stride, int ref_dtype, const double *poses, const double *cur_pose_inv, double radius,
                 int32_t *counts, uint16_t *h, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
 
+/* ---- C_PROTO refiner, first stage (csrc/cproto.hip): cpd/unsupervised_core/c_proto_refine.py:65-195
+ * compute_css_score_and_raw_proto for n_segments <= 1022 SEGMENTS, a segment = one (frame, box) pair of a chunk of frames. Ground
+ * removal and DBSCAN between cpd_cproto_filter and cpd_cproto_score are cpd_outline_ground / cpd_outline_dbscan with
+ * n_frames = n_segments + 1 and frame_off = filt_off. All arrays are DEVICE memory unless marked HOST. Caller-owned workspace; no
+ * allocation, no read-back, no host synchronisation inside a call. */
+size_t cpd_cproto_crop_workspace_bytes(int n_segments);
+/* Radius crop (l.120-123), counting pass. points / is_half / row_stride / frame_off / n_frames as in cpd_outline_ground; boxes
+ * [n_segments][7] float64; seg_frame [n_segments] the frame of each segment. A row of the segment's frame is kept when
+ * sqrt(dx*dx + dy*dy) < max(box[3], box[4]) in float64 (strict). seg_off [n_segments + 1]: row offsets of the segments' slices;
+ * seg_off[n_segments] is the total the caller reads to size the buffers of the calls below. */
+int cpd_cproto_crop_count(const void *points, int is_half, int row_stride, const int32_t *frame_off, int n_frames,
+                          const double *boxes, const int32_t *seg_frame, int n_segments, int32_t *seg_off, void *workspace,
+                          size_t workspace_bytes, cpd_stream_t stream);
+/* Radius crop, filling pass: the kept rows in input order, x y z in the input dtype, to out_rows [n_rows][3] and their row
+ * within the frame to out_src [n_rows]; n_rows = seg_off[n_segments] (rows past n_rows are never written). */
+int cpd_cproto_crop_fill(const void *points, int is_half, int row_stride, const int32_t *frame_off, int n_frames,
+                         const double *boxes, const int32_t *seg_frame, int n_segments, const int32_t *seg_off, int n_rows,
+                         void *out_rows, int32_t *out_src, cpd_stream_t stream);
+size_t cpd_cproto_filter_workspace_bytes(int n_segments, int n_rows);
+/* smooth_points (outline_utils.py:391-396) and the height window (l.125-147) over the crop (rows / seg_off / crop_src = the
+ * crop's out_rows / seg_off / out_src). dens_mask [n_rows]: 1 where more than 3 rows of the same segment, the row itself
+ * included, lie within float64 (dx*dx + dy*dy) + dz*dz <= radius*radius. z_min [S]: the least z of the dense rows, or
+ * box[2] - box[5] / 2 where there are none; new_box [S][7] = [x, y, h/2 + z_min, l, w, h, yaw] with h = max(box[2] + box[5]/2 -
+ * z_min, 1.3), where the clamp applies and dense rows exist h/2 + z_min is the sum in the input dtype (numpy 2 adds
+ * the Python float 0.65 to the z_min scalar in its dtype); had_points [S]: 1 where dense rows exist. filt_rows [n_rows][3] (input dtype) / filt_src [n_rows] (row within
+ * the frame): the dense rows with z > T(z_min + 0.2) (the sum rounded to the input dtype) and float64 z < box[2] + box[5]/2,
+ * order kept, segment s at filt_off[s] .. filt_off[s + 1]. filt_off has n_segments + 2 entries: the rows from
+ * filt_off[n_segments] to n_rows = filt_off[n_segments + 1] are zeroed and form one more segment, which holds no non-ground
+ * row, so that the calls that follow keep n_points = n_rows without a read-back. */
+int cpd_cproto_filter(const void *rows, int is_half, const int32_t *seg_off, const int32_t *crop_src, const double *boxes,
+                      int n_segments, int n_rows, double radius, uint8_t *dens_mask, double *z_min, double *new_box,
+                      int32_t *had_points, void *filt_rows, int32_t *filt_src, int32_t *filt_off, void *workspace,
+                      size_t workspace_bytes, cpd_stream_t stream);
+size_t cpd_cproto_score_workspace_bytes(int n_segments, int n_rows);
+/* The cluster the reference scores (clustering l.789-807, l.151-159) and compute_confidence's cell counts (l.398-436).
+ * ng_xyz / ng_src / ng_count = cpd_outline_ground's out_xyz / out_src / out_count, labels / n_clusters = cpd_outline_dbscan's.
+ * A segment scores when had_points, ng_count > min_rows (the reference's 10) and a cluster with more than cluster_min_points rows and max z <
+ * discard_max_height exists; best_label [S] is the first such cluster of strictly greatest size (-1: none), best_count [S] its
+ * size. m [S][8] float32: rows 0 and 1 of the inverse box transform; for the chosen rows X = ((x*m00 + y*m01) + z*m02) + m03
+ * and Y likewise in float64, unfused. occ [S][n_parts]: for parts[p] (HOST, n_parts <= 4, each <= 16) the number of cells
+ * (i, j) with more than one row, -l/2 + i*(l/parts) <= X < -l/2 + (i+1)*(l/parts) and the same for Y with w (l, w of new_box).
+ * out_xyz [n_rows][3] / out_src [n_rows] (row within the frame): the chosen clusters' rows, segment s at out_off[s] ..
+ * out_off[s + 1] (out_off [n_segments + 1]). */
+int cpd_cproto_score(const float *ng_xyz, const int32_t *ng_src, const int32_t *filt_off, const int32_t *ng_count,
+                     const int32_t *labels, const int32_t *n_clusters, const int32_t *had_points, const int32_t *filt_src,
+                     const float *m, const double *new_box, int n_segments, int n_rows, const int32_t *parts, int n_parts,
+                     int min_rows, int cluster_min_points, double discard_max_height, int32_t *occ, int32_t *best_label,
+                     int32_t *best_count, int32_t *out_off, float *out_xyz, int32_t *out_src, void *workspace,
+                     size_t workspace_bytes, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
