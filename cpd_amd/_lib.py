@@ -168,6 +168,9 @@ SIGNATURES = {
     "cpd_cproto_score_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_cproto_score": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I3, _I, _I, _I, _D, _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_refine_fit_size": (_I, [_VP, _VP, _VP, _I, _VP, _I3, _I, ctypes.POINTER(_D), _VP, _VP]),
+    "cpd_refine_orient_drift_workspace_bytes": (_SZ, [_I]),
+    "cpd_refine_orient_drift": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 

@@ -10,7 +10,8 @@ cluster are the reference's (with ground_removal's argsort stable: the canonical
 of the closed-form float32 inverse of the box transform and the unfused float64 product (the reference leaves both to LAPACK /
 BLAS), which differ from the reference's on a few per cent of the boxes by one cell.
 
-Not provided: refine_box_size, refine_box_pos and C_PROTO.__call__ (they need correct_orientation and density_guided_drift).
+Not provided here: refine_box_size, refine_box_pos and C_PROTO.__call__ (they need correct_orientation and density_guided_drift):
+cpd_amd.cproto_refine's C_PROTO, a subclass of this one, has them.
 """
 import copy
 import ctypes
@@ -198,12 +199,7 @@ class CProtoGPU:
         if stages:
             back += [("seg_off", seg_off), ("crop_src", src), ("dens_mask", f["dens_mask"]), ("filt_off", f["filt_off"]),
                      ("filt_src", f["filt_src"]), ("ng_count", cnt), ("ng_src", ng_src), ("labels", labels)]
-        host = torch.cat([t.reshape(-1).view(torch.uint8) for _, t in back]).cpu().numpy()   # the one copy back
-        res, o = {}, 0
-        for name, t in back:
-            nbytes = t.numel() * t.element_size()
-            res[name] = host[o:o + nbytes].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape))
-            o += nbytes
+        res = _copy_back(back)
         if int(res["err"][0]):
             raise _lib.CpdHipError("cpd_outline_ground: segment index outside the table")
         oo = res["out_off"]
@@ -242,6 +238,31 @@ class CProtoGPU:
             vals = [p[k] for p in parts]
             out[k] = sum(vals, []) if isinstance(vals[0], list) else np.concatenate(vals, 0)
         return out
+
+
+def _copy_back(back):
+    """[(name, device tensor)] -> {name: host array} through one device-to-host copy."""
+    torch, _, _ = _gpu_modules()
+    host = torch.cat([t.reshape(-1).view(torch.uint8) for _, t in back]).cpu().numpy()
+    res, o = {}, 0
+    for name, t in back:
+        nbytes = t.numel() * t.element_size()
+        res[name] = host[o:o + nbytes].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape))
+        o += nbytes
+    return res
+
+
+def _prefetched_chunks(paths, chunk):
+    """(first index, frames) per chunk of `chunk` .npy files; the next chunk's reads overlap the caller's work on this one."""
+    read = lambda c: [np.load(p)[:, 0:3] for p in c]
+    with ThreadPoolExecutor(4) as pool:
+        starts = list(range(0, len(paths), chunk))
+        fut = pool.submit(read, paths[:chunk]) if starts else None
+        for k, c in enumerate(starts):
+            frames = fut.result()
+            if k + 1 < len(starts):
+                fut = pool.submit(read, paths[starts[k + 1]:starts[k + 1] + chunk])
+            yield c, frames
 
 
 _GPU = {}
@@ -454,15 +475,8 @@ class C_PROTO():
         with open(self._path(''), 'rb') as f:
             outline_infos = pkl.load(f)
         paths = [os.path.join(self.root_path, self.seq_name, str(i).zfill(4) + '.npy') for i in range(len(outline_infos))]
-        read = lambda c: [np.load(p)[:, 0:3] for p in c]
-        with ThreadPoolExecutor(4) as pool:
-            chunks = [(c, paths[c:c + self.chunk]) for c in range(0, len(paths), self.chunk)]
-            fut = pool.submit(read, chunks[0][1]) if chunks else None
-            for k, (c, _) in enumerate(chunks):
-                frames = fut.result()
-                if k + 1 < len(chunks):   # the next chunk's reads overlap this chunk's kernels
-                    fut = pool.submit(read, chunks[k + 1][1])
-                self.score_frames(frames, outline_infos[c:c + len(frames)], raw_proto_set)
+        for c, frames in _prefetched_chunks(paths, self.chunk):   # the next chunk's reads overlap this chunk's kernels
+            self.score_frames(frames, outline_infos[c:c + len(frames)], raw_proto_set)
         with open(output_pkl_path, 'wb') as f:
             pkl.dump(outline_infos, f)
         with open(output_raw_proto_path, 'wb') as f:

@@ -927,6 +927,35 @@ int cpd_cproto_score(const float *ng_xyz, const int32_t *ng_src, const int32_t *
                      int32_t *best_count, int32_t *out_off, float *out_xyz, int32_t *out_src, void *workspace,
                      size_t workspace_bytes, cpd_stream_t stream);
 
+/* ---- C_PROTO refiner, second stage (csrc/cproto_refine.hip): cpd/unsupervised_core/c_proto_refine.py:332-475 refine_box_size on
+ * the segments of the first stage (n_segments <= 1022). The launch order is crop, filter, cpd_refine_fit_size, ground, dbscan,
+ * score, cpd_refine_orient_drift. All arrays are DEVICE memory unless marked HOST. Caller-owned workspace; no allocation, no
+ * read-back, no host synchronisation inside a call. */
+/* The prototype size fit (l.410-436). new_box [S][7] is cpd_cproto_filter's output, updated in place; seg_cls [S]: 0 Vehicle,
+ * 1 Pedestrian, 2 Cyclist (any other value: fit_index -1, the row untouched); basic_whl [S][3]: the whl of
+ * basic_proto_set[cls][proto_id] where the box's own id is a basic prototype, a NaN row otherwise. hq_whl [3][cap][3]: each
+ * class's high-quality prototype whl in the file's insertion order, hq_count (HOST [3]) of them, cap <= 64; predefined
+ * (HOST [3][3]): PredifinedSize per class. fit_index [S]: -2 the own basic prototype (l.415-417); k >= 0 the first minimum of
+ * |hq_whl[cls][k][2] - h|, h = new_box[5] (np.argmin, l.428); -1 the predefined size, where the class has no high-quality
+ * prototype (l.423-426). Only Vehicle rows get new_box[3], new_box[4] overwritten with the fitted size (l.433-436).
+ * CPD_ERR_UNSUPPORTED: cap outside 1..64; CPD_ERR_ARG: a count outside 0..cap, n_segments > 1022. */
+int cpd_refine_fit_size(double *new_box, const int32_t *seg_cls, const double *basic_whl, int n_segments, const double *hq_whl,
+                        const int32_t *hq_count, int cap, const double *predefined, int32_t *fit_index, cpd_stream_t stream);
+size_t cpd_refine_orient_drift_workspace_bytes(int n_segments);
+/* correct_orientation (outline_utils.py:127-326) and density_guided_drift (outline_utils.py:41-92) on the chosen clusters:
+ * out_xyz / out_off / best_label are cpd_cproto_score's, new_box [S][7] the fitted boxes, m [S][8] float32 rows 0 and 1 of the
+ * inverse box transform. Box-frame coordinates X = ((x*m00 + y*m01) + z*m02) + m03 and Y likewise in float64, unfused; the
+ * forward transform's cos yaw, sin yaw, x, y are rounded to float32 (the reference's float32 trans_mat). box_drift [S][7] =
+ * density_guided_drift(cluster, box); box_orient [S][7] = correct_orientation(cluster, box): the 2 x 7 bins (mid + i*delta, mid +
+ * (i+1)*delta] and (min + i*delta, min + (i+1)*delta] along x when ((max_x-min_x)/l)*2 > (max_y-min_y)/w (strict), else along y,
+ * per bin the row of greatest (more than half of all rows positive) or least other coordinate, ties to the lowest row, yaw +=
+ * arctan of the slope between the means of the picked rows; box_orient_drift [S][7] = density_guided_drift(cluster,
+ * box_orient), with the inverse of the re-oriented transform formed on the device (closed form over the float32 entries, rounded
+ * to float32). All three equal new_box where best_label < 0. The workspace holds the re-oriented inverse rows. */
+int cpd_refine_orient_drift(const float *out_xyz, const int32_t *out_off, const int32_t *best_label, const double *new_box,
+                            const float *m, int n_segments, int n_rows, double *box_drift, double *box_orient_drift,
+                            double *box_orient, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
