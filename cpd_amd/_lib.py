@@ -171,6 +171,12 @@ SIGNATURES = {
     "cpd_refine_fit_size": (_I, [_VP, _VP, _VP, _I, _VP, _I3, _I, ctypes.POINTER(_D), _VP, _VP]),
     "cpd_refine_orient_drift_workspace_bytes": (_SZ, [_I]),
     "cpd_refine_orient_drift": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_mfcf_gather_workspace_bytes": (_SZ, [_I]),
+    "cpd_mfcf_gather": (_I, [_VP, _VP, _I3, _I3, _I3, ctypes.POINTER(_D), _I, _I3, _I3, _I3, ctypes.POINTER(_D), _I3, _I, _F, _VP,
+                             _VP, _VP, _SZ, _VP]),
+    "cpd_mfcf_voxel_sample_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_mfcf_voxel_sample": (_I, [_VP, _VP, _VP, _I, _I, _F, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_mfcf_fit_dgd": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
 }
 
 

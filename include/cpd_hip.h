@@ -956,6 +956,56 @@ int cpd_refine_orient_drift(const float *out_xyz, const int32_t *out_off, const 
                             const float *m, int n_segments, int n_rows, double *box_drift, double *box_orient_drift,
                             double *box_orient, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
 
+/* ---- MFCF pseudo-label generator, per-frame half (csrc/mfcf.hip): cpd/unsupervised_core/mfcf.py:46-80 for a chunk of current
+ * frames. The launch order is cpd_mfcf_gather, cpd_mfcf_voxel_sample, cpd_outline_ground (float32), cpd_outline_dbscan,
+ * cpd_outline_boxes, cpd_mfcf_fit_dgd. All arrays are DEVICE memory unless marked HOST. Caller-owned workspace; no allocation, no
+ * read-back, no host synchronisation inside a call. */
+size_t cpd_mfcf_gather_workspace_bytes(int max_rows);
+/* The aggregation (mfcf.py:53-72). n_sweeps uploaded sweeps: sweep_pts (HOST [n_sweeps] device pointers to rows of
+ * sweep_stride[s] >= 3 elements, float32 (sweep_dtype[s] = 0) or float16 (1), x y z first), sweep_h (HOST [n_sweeps] device
+ * pointers to float16 PP scores, sweep_rows[s] each), sweep_pose (HOST [n_sweeps][16] row-major sweep -> world). Current frame
+ * f: its window is sweeps win_sweep[f][0 .. win_count[f]) (HOST [n_frames][16], loop order, win_count <= 16), its own sweep
+ * cur_sweep[f], cur_pose_inv (HOST [n_frames][16]) the inverse of its pose. out [out_off[n_frames]][3] float32: frame f's slice
+ * starts at row out_off[f] (HOST [n_frames + 1], out_off[0] = 0, each slice at least the window's rows plus the current sweep's)
+ * and holds out_count[f] (DEVICE) rows: of every window sweep in order the rows with H > thresh, taken sweep -> world -> current
+ * frame by the two products of cpd_ppscore (float64 accumulation in the reference's order, each rounded to float32, l.63, 69),
+ * then the current sweep's own rows converted to float32 (l.72). thresh is the threshold as numpy rounds it against a float16
+ * array (l.71); both sides are compared exactly and a NaN score is dropped. max_rows for the workspace: the largest
+ * window-plus-current row count. CPD_ERR_UNSUPPORTED: a window of more than 16 sweeps. */
+int cpd_mfcf_gather(const void *const *sweep_pts, const void *const *sweep_h, const int32_t *sweep_rows,
+                    const int32_t *sweep_stride, const int32_t *sweep_dtype, const double *sweep_pose, int n_sweeps,
+                    const int32_t *win_sweep, const int32_t *win_count, const int32_t *cur_sweep, const double *cur_pose_inv,
+                    const int32_t *out_off, int n_frames, float thresh, float *out, int32_t *out_count, void *workspace,
+                    size_t workspace_bytes, cpd_stream_t stream);
+size_t cpd_mfcf_voxel_sample_workspace_bytes(int n_frames, int n_points);
+/* voxel_sampling (outline_utils.py:368-389) per frame: frame f = rows frame_off[f] .. frame_off[f] + frame_count[f] of points
+ * [n_points][3] float32 (frame_off [n_frames + 1], frame_count [n_frames]; frame_off[f + 1] - frame_off[f] >= frame_count[f]).
+ * The cell of a row is (x - min) // res per axis in float32 with numpy's floor_divide (the quotient of the fmod-reduced
+ * numerator, floored, with its half-ulp correction), min the least coordinate of the frame; cells come out in the order of
+ * their first row, each with the coordinates of its LAST row (a dict keyed by cell, values overwritten). out [n_points][3]
+ * and out_src [n_points] (that row's index within its frame; may be NULL):
+ * frame f's rows at out_off[f] .. out_off[f + 1], back to back; out_off has n_frames + 2 entries: the rows from
+ * out_off[n_frames] to n_points = out_off[n_frames + 1] are zero and form one more frame, which holds no non-ground row, so that
+ * the calls that follow take n_frames + 1 frames and n_points rows without a read-back. *err |= 1 where a coordinate is NaN or a
+ * cell index does not fit 21 bits (CPD_ERR_UNSUPPORTED, reported by the caller after its one copy back), |= 2 where a slice
+ * runs past n_points (its rows are left out). */
+int cpd_mfcf_voxel_sample(const float *points, const int32_t *frame_off, const int32_t *frame_count, int n_frames, int n_points,
+                          float res, float *out, int32_t *out_src, int32_t *out_off, int32_t *err, void *workspace,
+                          size_t workspace_bytes, cpd_stream_t stream);
+/* box_fit_DGD's tail (outline_utils.py:881-883) on boxes = cpd_outline_boxes' out (box_cap as there; xyz, frame_off,
+ * frame_count, labels as there): for box k of frame f and cluster c the rows of the frame with label c and z > min z + 0.2
+ * (box_fit's filter, l.853-856) go through density_guided_drift (l.41-92), then correct_orientation (l.127-326), then
+ * correct_heading (l.444-485: ten slabs -l/2 + i*(l/10) <= X < -l/2 + (i+1)*(l/10), per non-empty slab the greatest box-frame
+ * z, the mean over the slabs whose lower bound is < 0 against the mean over those whose upper bound is > 0, 0 for none, yaw +=
+ * pi where the first is smaller), each step on the closed-form float32 inverse of the box the step before left (arithmetic as
+ * cpd_refine_orient_drift). steps: 1 drift | 2 orientation | 4 heading select the steps that run (7: box_fit_DGD; the one-call
+ * forms run one), | 8 takes every row of the cluster, without the height filter. out [box_cap][7]. bits [box_cap]: 1 drift took
+ * the max side on x, 2 on y, 4 orientation binned along x, 8 it took the maxima, 16 it turned the box, 32 the heading was
+ * flipped. n_out [1]: min(boxes, box_cap). One workgroup per box, any number of boxes. */
+int cpd_mfcf_fit_dgd(const float *xyz, const int32_t *frame_off, const int32_t *frame_count, int n_frames, int n_points,
+                     const int32_t *labels, const double *boxes, int box_cap, int steps, double *out, int32_t *bits,
+                     int32_t *n_out, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
