@@ -779,14 +779,20 @@ def boxes_iou_bev_cpu(a, b):
     return out
 
 
-def gather_conv_tile(n_out, c_in, c_out, in_ld, dense=False, bf16x3=False, nbr=None, math=None, scaled=False, in_pairs=False):
+RW_TAPS = 28                 # CPD_RW_TAPS of csrc/gather_conv.hip: the most taps a row-wave launch takes
+
+
+def gather_conv_tile(n_out, c_in, c_out, in_ld, dense=False, bf16x3=False, nbr=None, math=None, scaled=False, in_pairs=False, kv=None):
     """Name of the kernel instantiation gather_conv will run for this problem (`nbr`: the table it would be given; `scaled`: an
-    `in_absmax` block comes with the input -- the split-fp16 kernels then run as their pre-scaling `f16s` instantiations)."""
+    `in_absmax` block comes with the input -- the split-fp16 kernels then run as their pre-scaling `f16s` instantiations; `kv`: the
+    tap count, when known -- a kernel with more taps than the row-wave kernels keep is planned as a dense layer, as the launcher does)."""
     if nbr is not None and getattr(nbr, "plan", None) is not None and not scaled and lib().cpd_gather_conv_planned_supported(
             int(nbr.shape[1]), int(n_out), int(c_in), int(c_out), int(in_ld), int(nbr.shape[0]),
             _gc_flags(dense, bf16x3, math) | (16 if in_pairs else 0) | 32):      # (the staged kernel writes pair rows)
         return "rowplan_conv_f16p_kernel<%d%s>" % (c_out, ",256" if nbr.plan[3] == 256 else "")
     name = _gather_conv_tile(n_out, c_in, c_out, in_ld, dense, bf16x3, nbr, math, in_pairs)
+    if kv is not None and kv > RW_TAPS and name.startswith("rowwave_conv_"):
+        name = _gather_conv_tile(n_out, c_in, c_out, in_ld, True, bf16x3, nbr, math, in_pairs)
     return name.replace("_f16_kernel", "_f16s_kernel") if scaled else name
 
 
