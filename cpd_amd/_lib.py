@@ -177,6 +177,7 @@ SIGNATURES = {
     "cpd_mfcf_voxel_sample_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_mfcf_voxel_sample": (_I, [_VP, _VP, _VP, _I, _I, _F, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_mfcf_fit_dgd": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "cpd_oyster_align_tracks": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
 }
 
 

@@ -1006,6 +1006,24 @@ int cpd_mfcf_fit_dgd(const float *xyz, const int32_t *frame_off, const int32_t *
                      const int32_t *labels, const double *boxes, int box_cap, int steps, double *out, int32_t *bits,
                      int32_t *n_out, cpd_stream_t stream);
 
+/* ---- OYSTER pseudo-label generator (csrc/oyster.hip): the per-track size consensus of cpd/unsupervised_core/oyster.py:89-115
+ * and corner_align (outline_utils.py:94-123) for every qualifying track of a sequence in one launch. boxes [n_rows][7] float64
+ * (x y z l w h yaw) in track-major order, each track's rows in frame order; track t is rows track_off[t] .. track_off[t + 1]
+ * (track_off [n_tracks + 1], DEVICE like every array here, non-decreasing, within 0..n_rows: the caller checks it on the host
+ * before the upload; a track whose offsets break that is skipped untouched). track_top [n_tracks]: max(3, int(n * (1 - 0.95)))
+ * as Python evaluates it for the track's n rows (1 - 0.95 is 0.050000000000000044), computed on the host; clamped to 1..n.
+ * Per track: dis = sqrt((x*x + y*y) + z*z), rows ordered ascending by dis (ties to the lower row, NaN last), mean_l / mean_w
+ * the sums of l / w over the track_top nearest rows added one after another in that order (np.mean(axis=0)), divided by
+ * their number. Per row: l_off = mean_l - l, w_off = mean_w - w; the candidates (l_off/2, w_off/2), (-, -), (+, -), (-, +) go
+ * through the box's pose with cos yaw, sin yaw, x, y, z rounded to float32 (the reference's float32 trans_mat) and the products
+ * and sums in float64, unfused; the candidate of the GREATEST norm of (x', y', z', 1) is taken (the reference's arg_min is an
+ * argmax), the first on ties. out [n_rows][7] (not overlapping boxes): x y of that candidate, z = float32(z), l + l_off,
+ * w + w_off, h and yaw as they came. Rows outside every track are not written. One workgroup per track, any track length, any
+ * number of tracks; no workspace, no allocation, no read-back. n_tracks == 0 or n_rows == 0: CPD_OK without a launch.
+ * CPD_ERR_ARG: a negative count, a null pointer. */
+int cpd_oyster_align_tracks(const double *boxes, const int32_t *track_off, const int32_t *track_top, int n_tracks, int n_rows,
+                            double *out, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
