@@ -6,8 +6,10 @@
 //   maps at the winners -> exp(dim), atan2(sin, cos), centre scaling -> POST_CENTER_LIMIT_RANGE
 //   and SCORE_THRESH masks -> order-preserving compaction (scores stay sorted descending).
 // The reference runs this as ~20 small torch kernels; here it is two launches:
-//   topk_class_kernel : one 1024-thread workgroup per class: 4-pass radix select of the K-th key
-//                       (LDS histogram), ordered tie collection, 1024-wide bitonic sort in LDS
+//   topk_class_kernel : one 1024-thread workgroup per class: a logit histogram picks <= 1024 candidates
+//                       (block_topk_logits); where that cannot keep the tie rule or they do not fit, a
+//                       4-pass radix select of the K-th key (LDS histogram) with ordered tie collection
+//                       (block_topk); either way a 1024-wide bitonic sort in LDS
 //   decode_kernel     : one workgroup: second top-K, gather, decode, mask, block-scan compaction
 // Ties are broken by ascending flat index (torch.topk leaves tie order unspecified).
 #include "common.h"
@@ -119,6 +121,20 @@ __device__ void block_topk(int n, int K, KeyFn keyfn, TopkSmem &sm) {
 // suffix scan to the bin holding the K-th element, then an exact bitonic sort of the <= 1024
 // candidates above it on their sigmoid keys. Falls back to the exact radix select when the
 // candidate set does not fit (degenerate score distributions).
+//
+// The order promised is (sigmoid key descending, index ascending), and bins are cut on the LOGIT: a pixel left out must not
+// carry the K-th key, or its lower index would have won. fp32 sigmoid is flat over many logits (neighbouring positive floats share
+// a value, a whole bin width of 40/2048 does from x ~ 12.7 up, everything from ~16.7 is 1.0f), so with b* the bin of the K-th
+// logit the candidates are the bins >= b* - 1, and the path is taken only for b* <= TOPK_BIN_MAX, the bin whose lower edge is
+// x = 10. A pixel left out then has x < edge(b* - 1) < lo and the K-th logit has x_K >= edge(b*) > hi, with lo / hi a quarter
+// bin inside the two edges (the rounding in logit_bin moves an edge by ~1e-5, a quarter bin is 5e-3). A quarter bin changes
+// exp(-x) by 0.5 %, far beyond expf's rounding, so expf(-x) > expf(-lo) and expf(-x_K) < expf(-hi) as computed; 1 + e and
+// 1 / y round monotonically; hence key(x) <= key(lo) and key(hi) <= key(x_K). And key(lo) < key(hi): they are half a bin,
+// 40/4096, apart and hi <= 10, where sigmoid' = s (1 - s) >= 4.5e-5, so the true values differ by >= 4.4e-7 = 7.4 steps of
+// 2^-24 (fp32's spacing in [0.5, 1), the coarsest a sigmoid value meets), while a computed value is within 1.5 steps of the true
+// one there (half an ulp of 1 + e in [1, 2), carried through 1 / y, plus the division's own half ulp; expf's error on e ~ 5e-5 is
+// ~1e-11); for smaller x the difference grows with 1 - s and the spacing only shrinks. So no tie crosses the cut.
+// Above bin TOPK_BIN_MAX (heads that saturate: scores over 0.99995) the radix path, which selects on the keys themselves, runs.
 struct TopkHist {
     uint32_t hist[2048];
     uint32_t cnt, bstar, ok;
@@ -128,6 +144,7 @@ __device__ __forceinline__ int logit_bin(float x) {
     t = t < 0.f ? 0.f : (t > 2047.f ? 2047.f : t);
     return (x != x) ? 0 : (int)t;
 }
+constexpr int TOPK_BIN_MAX = 1536;         // (10 + 20) * 51.2
 __device__ bool block_topk_logits(const MapView &hm, int cls, int n, int K, TopkHist &h, TopkSmem &sm) {
     const int tid = threadIdx.x, nth = blockDim.x;
     for (int b = tid; b < 2048; b += nth) h.hist[b] = 0;
@@ -147,8 +164,9 @@ __device__ bool block_topk_logits(const MapView &hm, int cls, int n, int K, Topk
                 c += h.hist[b];
                 if (c >= (uint32_t)K) break;
             }
-            h.bstar = (uint32_t)b;
-            h.ok = c <= 1024u ? 1u : 0u;       // candidates = everything in bins >= b*
+            if (b > 0) c += h.hist[b - 1];     // candidates = everything in bins >= b* - 1 (see above)
+            h.bstar = (uint32_t)(b > 0 ? b - 1 : 0);
+            h.ok = (c <= 1024u && b <= TOPK_BIN_MAX) ? 1u : 0u;
         }
     }
     __syncthreads();
