@@ -17,9 +17,10 @@ import copy
 import ctypes
 import os
 import pickle as pkl
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+
+from .seq_io import _get, dtype_runs, frame_path, gpu_modules, prefetched_chunks, run_sequences
 
 # GeneratorConfig / RefinerConfig of tools/cfgs/dataset_configs/waymo_unsupervised/waymo_unsupervised_cproto.yaml (the keys the
 # first stage reads)
@@ -42,12 +43,6 @@ CLASSES = ('Vehicle', 'Pedestrian', 'Cyclist')
 # cpd_cproto_filter): 128 segments keep the ground workspace at 106 MB.
 SUB_BATCH = 128
 MAX_PARTS, MAX_PART = 4, 16      # cproto.hip CP_MAX_PARTS, CP_MAX_PART
-
-
-def _get(cfg, name, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(name, default)
-    return getattr(cfg, name, default)
 
 
 def KL_entropy_score(x, y, max_dif=0.05):
@@ -85,18 +80,12 @@ def inverse_box_rows(boxes):
     return np.ascontiguousarray(m.astype(np.float32))
 
 
-def _gpu_modules():
-    import torch
-    from . import _lib, outline
-    return torch, _lib, outline
-
-
 class CProtoGPU:
     """The launch sequence of the first stage on one device. Frames go in as [N_i, >=3] float16 / float32 arrays of one
     dtype, segments as boxes [S, 7] float64 (after the size overwrite) with the frame each belongs to."""
 
     def __init__(self, config=None, device=None, sub_batch=SUB_BATCH):
-        torch, _lib, outline = _gpu_modules()
+        from . import outline
         config = CPROTO_CONFIG if config is None else config
         gcfg, rcfg = _get(config, "GeneratorConfig"), _get(config, "RefinerConfig")
         params = outline._params(gcfg, ground_min_threshold=list(_get(rcfg, "GroundMin")))
@@ -122,7 +111,7 @@ class CProtoGPU:
 
     # -- stages (device tensors in, device tensors out) --
     def crop(self, pts, off, n_frames, boxes, seg_frame):
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         lib, S, dev = _lib.lib(), int(boxes.shape[0]), self.device
         is_half = 1 if pts.dtype == torch.float16 else 0
         seg_off = torch.empty(S + 1, dtype=torch.int32, device=dev)
@@ -139,7 +128,7 @@ class CProtoGPU:
         return rows, src, seg_off, n_rows
 
     def filter(self, rows, src, seg_off, boxes, n_rows, radius=0.2):
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         lib, S, dev = _lib.lib(), int(boxes.shape[0]), self.device
         out = dict(dens_mask=torch.empty(max(n_rows, 1), dtype=torch.uint8, device=dev),
                    z_min=torch.empty(max(S, 1), dtype=torch.float64, device=dev),
@@ -159,7 +148,7 @@ class CProtoGPU:
 
     def score(self, xyz, ng_src, off, cnt, labels, ncl, had, filt_src, m, new_box, S, n_rows, min_rows=10,
               cluster_min_points=None, discard_max_height=None):
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         lib, dev = _lib.lib(), self.device
         P = len(self.parts)
         out = dict(occ=torch.empty((max(S, 1), P), dtype=torch.int32, device=dev),
@@ -181,7 +170,7 @@ class CProtoGPU:
 
     # -- one sub-batch: every launch, then one copy back --
     def _run_sub(self, pts, off, n_frames, boxes, seg_frame, stages):
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         dev = self.device
         S = len(boxes)
         d_boxes = torch.from_numpy(np.ascontiguousarray(boxes, np.float64)).to(dev)
@@ -242,7 +231,7 @@ class CProtoGPU:
 
 def _copy_back(back):
     """[(name, device tensor)] -> {name: host array} through one device-to-host copy."""
-    torch, _, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     host = torch.cat([t.reshape(-1).view(torch.uint8) for _, t in back]).cpu().numpy()
     res, o = {}, 0
     for name, t in back:
@@ -252,24 +241,11 @@ def _copy_back(back):
     return res
 
 
-def _prefetched_chunks(paths, chunk):
-    """(first index, frames) per chunk of `chunk` .npy files; the next chunk's reads overlap the caller's work on this one."""
-    read = lambda c: [np.load(p)[:, 0:3] for p in c]
-    with ThreadPoolExecutor(4) as pool:
-        starts = list(range(0, len(paths), chunk))
-        fut = pool.submit(read, paths[:chunk]) if starts else None
-        for k, c in enumerate(starts):
-            frames = fut.result()
-            if k + 1 < len(starts):
-                fut = pool.submit(read, paths[starts[k + 1]:starts[k + 1] + chunk])
-            yield c, frames
-
-
 _GPU = {}
 
 
 def _gpu(device=None):
-    torch, _, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     dev = torch.device(device if device is not None else "cuda")
     key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     g = _GPU.get(key)
@@ -291,7 +267,7 @@ def _device_points(points):
 
 def smooth_points(points, rad=0.2, device=None):
     """outline_utils.py:391-396 on the GPU: the rows with more than 3 rows (itself included) within rad."""
-    torch, _, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     points = np.asarray(points)
     n = len(points)
     if n == 0:
@@ -306,7 +282,7 @@ def smooth_points(points, rad=0.2, device=None):
 
 
 def _occupancy(points, box, parts, device=None):
-    torch, _, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     g = _gpu(device)
     pts = np.ascontiguousarray(_device_points(np.asarray(points))[:, 0:3].astype(np.float32))
     n, dev = len(pts), g.device
@@ -379,18 +355,6 @@ class CSS():
         return self.compute_css(points, box, name)
 
 
-def _dtype_runs(frames, chunk):
-    """Runs of at most `chunk` consecutive frames of one dtype (the ground projection's arithmetic is per dtype)."""
-    runs, c0 = [], 0
-    while c0 < len(frames):
-        c1 = c0 + 1
-        while c1 < len(frames) and c1 - c0 < chunk and frames[c1].dtype == frames[c0].dtype:
-            c1 += 1
-        runs.append((c0, c1))
-        c0 = c1
-    return runs
-
-
 class C_PROTO():
     """c_proto_refine.py:46-330: the same files (<seq>_outline_<Init>.pkl in, <seq>_outline_<Init>_CSS.pkl and
     _CSS_raw_proto.pkl out, cached; construct_prototypes: _CSS_proto.pkl)."""
@@ -413,13 +377,18 @@ class C_PROTO():
         init = str(_get(self.dataset_cfg, "InitLabelGenerator"))
         return os.path.join(self.root_path, self.seq_name, self.seq_name + '_outline_' + init + suffix + '.pkl')
 
+    def frame_chunks(self, n):
+        """(indices, frames) per chunk of the sequence's n frame files; the next chunk's reads overlap this chunk's kernels."""
+        seq_dir = os.path.join(self.root_path, self.seq_name)
+        return prefetched_chunks([frame_path(seq_dir, i) for i in range(n)], self.chunk)
+
     def score_frames(self, frames, infos, raw_proto_set, stages=None):
         """l.91-188 for the frames (a list of [N, 3] arrays) that go with infos (updated in place)."""
         css = self.css_estimator
         thresh = _get(_get(self.dataset_cfg, "RefinerConfig"), "BasicProtoScoreThresh")
         seq_id = int(self.seq_name[8:16])
         frames = [np.asarray(f) for f in frames]
-        for c0, c1 in _dtype_runs(frames, self.chunk):
+        for c0, c1 in dtype_runs(frames, self.chunk):
             boxes, seg_frame, where = [], [], []
             for i in range(c0, c1):     # the size overwrite (l.111-118); classes outside the three are skipped
                 for b in range(len(infos[i]['outline_box'])):
@@ -474,9 +443,8 @@ class C_PROTO():
                 return pkl.load(f)
         with open(self._path(''), 'rb') as f:
             outline_infos = pkl.load(f)
-        paths = [os.path.join(self.root_path, self.seq_name, str(i).zfill(4) + '.npy') for i in range(len(outline_infos))]
-        for c, frames in _prefetched_chunks(paths, self.chunk):   # the next chunk's reads overlap this chunk's kernels
-            self.score_frames(frames, outline_infos[c:c + len(frames)], raw_proto_set)
+        for idx, frames in self.frame_chunks(len(outline_infos)):
+            self.score_frames(frames, outline_infos[idx[0]:idx[0] + len(frames)], raw_proto_set)
         with open(output_pkl_path, 'wb') as f:
             pkl.dump(outline_infos, f)
         with open(output_raw_proto_path, 'wb') as f:
@@ -586,12 +554,8 @@ def construct_prototypes(raw_proto_set, refiner_cfg):
 def create_css(seq_names, root_path, dataset_cfg, device=None, chunk=16):
     """Single-process sequence driver (forked workers must not each open the GPU): every sequence's
     compute_css_score_and_raw_proto and construct_prototypes through one GPU context."""
-    out, gpu = [], None
-    for s in seq_names:
-        c = C_PROTO(s, root_path, dataset_cfg, device, chunk)
-        c._gpu = gpu
+    def run(c):
         infos = c.compute_css_score_and_raw_proto()
-        gpu = c._gpu
         c.construct_prototypes()
-        out.append(infos)
-    return out
+        return infos
+    return run_sequences(lambda s: C_PROTO(s, root_path, dataset_cfg, device, chunk), seq_names, run)

@@ -17,8 +17,8 @@ import pickle as pkl
 import numpy as np
 
 from . import cproto
-from .cproto import (CLASSES, _copy_back, _dtype_runs, _get, _gpu_modules, _prefetched_chunks, inverse_box_rows,
-                     points_rigid_transform)
+from .cproto import CLASSES, _copy_back, inverse_box_rows, points_rigid_transform
+from .seq_io import _get, dtype_runs, gpu_modules, run_sequences
 
 # RefinerConfig of waymo_unsupervised_cproto.yaml with the two keys the second half reads
 REFINE_CONFIG = copy.deepcopy(cproto.CPROTO_CONFIG)
@@ -62,7 +62,7 @@ class RefineGPU(cproto.CProtoGPU):
     dbscan, score, orient_drift, one copy back."""
 
     def set_prototypes(self, table):
-        torch, _, _ = _gpu_modules()
+        torch, _ = gpu_modules()
         self.table = table
         self.d_hq_whl = torch.from_numpy(table.hq_whl).to(self.device)
         self.c_hq_count = (ctypes.c_int32 * 3)(*table.count)
@@ -71,7 +71,7 @@ class RefineGPU(cproto.CProtoGPU):
     # -- stages (device tensors in, device tensors out) --
     def fit_size(self, new_box, seg_cls, basic_whl, S):
         """new_box [S, 7] is updated in place; returns fit_index [S]."""
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         fit = torch.empty(max(S, 1), dtype=torch.int32, device=self.device)
         _lib.check(_lib.lib().cpd_refine_fit_size(_lib.ptr(new_box), _lib.ptr(seg_cls), _lib.ptr(basic_whl), S,
                                                   _lib.ptr(self.d_hq_whl), self.c_hq_count, self.table.cap, self.c_predefined,
@@ -79,7 +79,7 @@ class RefineGPU(cproto.CProtoGPU):
         return fit
 
     def orient_drift(self, out_xyz, out_off, best_label, new_box, m, S, n_rows):
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         lib, dev = _lib.lib(), self.device
         out = {k: torch.empty((max(S, 1), 7), dtype=torch.float64, device=dev)
                for k in ("box_drift", "box_orient_drift", "box_orient")}
@@ -95,7 +95,7 @@ class RefineGPU(cproto.CProtoGPU):
     def _run_sub(self, pts, off, n_frames, boxes, seg_frame, stages, seg_cls=None, basic_whl=None):
         if seg_cls is None:      # the first stage, unchanged
             return super()._run_sub(pts, off, n_frames, boxes, seg_frame, stages)
-        torch, _lib, _ = _gpu_modules()
+        torch, _lib = gpu_modules()
         dev = self.device
         S = len(boxes)
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
@@ -158,7 +158,7 @@ class RefineGPU(cproto.CProtoGPU):
 # ---- the two functions on one cluster (reference signatures) --------------------------------------------------------------------
 
 def _orient_drift_one(points, box, device=None):
-    torch, _, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     g = _gpu(device)
     pts = np.ascontiguousarray(cproto._device_points(np.asarray(points))[:, 0:3].astype(np.float32))
     box = np.asarray(box, np.float64).reshape(1, 7)
@@ -185,7 +185,7 @@ _GPU = {}
 
 
 def _gpu(device=None):
-    torch, _, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     dev = torch.device(device if device is not None else "cuda")
     key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     g = _GPU.get(key)
@@ -332,7 +332,7 @@ class C_PROTO(cproto.C_PROTO):
             gpu.set_prototypes(table)
         for i in range(len(frames)):
             infos[i]['outline_proto_id'] = np.ones_like(infos[i]['outline_ids'], dtype=np.longlong) * (-1)
-        for c0, c1 in _dtype_runs(frames, self.chunk):
+        for c0, c1 in dtype_runs(frames, self.chunk):
             boxes, seg_frame, seg_cls, basic, where = [], [], [], [], []
             for i in range(c0, c1):
                 for b in range(len(infos[i]['outline_box'])):
@@ -368,9 +368,8 @@ class C_PROTO(cproto.C_PROTO):
         with open(self._path('_CSS'), 'rb') as f:
             outline_infos = pkl.load(f)
         table = PrototypeTable(proto_set, self.css_estimator.predifined_size)
-        paths = [os.path.join(self.root_path, self.seq_name, str(i).zfill(4) + '.npy') for i in range(len(outline_infos))]
-        for c, frames in _prefetched_chunks(paths, self.chunk):   # the next chunk's reads overlap this chunk's kernels
-            self.resize_frames(frames, outline_infos[c:c + len(frames)], table)
+        for idx, frames in self.frame_chunks(len(outline_infos)):
+            self.resize_frames(frames, outline_infos[idx[0]:idx[0] + len(frames)], table)
         with open(output_info_path, 'wb') as f:
             pkl.dump(outline_infos, f)
         return outline_infos
@@ -397,10 +396,4 @@ class C_PROTO(cproto.C_PROTO):
 def create_refined(seq_names, root_path, dataset_cfg, device=None, chunk=16):
     """Single-process sequence driver (forked workers must not each open the GPU): every sequence's four stages through one
     GPU context. Returns the final infos per sequence."""
-    out, gpu = [], None
-    for s in seq_names:
-        c = C_PROTO(s, root_path, dataset_cfg, device, chunk)
-        c._gpu = gpu
-        out.append(c())
-        gpu = c._gpu
-    return out
+    return run_sequences(lambda s: C_PROTO(s, root_path, dataset_cfg, device, chunk), seq_names, lambda c: c())

@@ -57,6 +57,61 @@ static inline int cpd_zero_fill(void *p, size_t bytes, hipStream_t s) { return c
 static inline size_t cpd_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int cpd_div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// Workspace carving: consecutive 256-byte-aligned pieces of one buffer, as offsets; `o` ends as the total. ws_at turns an
+// offset into a pointer (null for a null buffer: the size-only pass of a layout function).
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) {
+        const size_t at = o;
+        o += cpd_align(bytes);
+        return at;
+    }
+};
+template <class T>
+static inline T *ws_at(void *ws, size_t off) {
+    return ws ? reinterpret_cast<T *>(static_cast<char *>(ws) + off) : nullptr;
+}
+
+// ---- small device helpers of the pseudo-label kernels (and decode.hip's top-K keys) ----
+__device__ __forceinline__ uint32_t float_key(float f) {      // order-preserving uint key of a float
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float float_unkey(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ float round_half(float v) { return (float)(_Float16)v; }   // round to float16 (nearest even)
+
+// row `row` of a [.][stride] float16 / float32 array as three floats (exact)
+__device__ __forceinline__ void load_xyz(const void *base, int is_half, int stride, long long row, float &x, float &y, float &z) {
+    if (is_half) {
+        const _Float16 *p = static_cast<const _Float16 *>(base) + row * stride;
+        x = (float)p[0], y = (float)p[1], z = (float)p[2];
+    } else {
+        const float *p = static_cast<const float *>(base) + row * stride;
+        x = p[0], y = p[1], z = p[2];
+    }
+}
+
+// largest s < n with off[s] <= i (off ascending: CSR frame / segment offsets in global memory)
+__device__ __forceinline__ int segment_of(const int32_t *off, int n, int i) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long k) {   // the 64-bit finaliser of MurmurHash3
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Device-wide exclusive scan over a virtual sequence value(i), i in [0,n), in three launches:
 //   scan_reduce  : per-block sums            (blocks of SCAN_BLOCK threads x SCAN_ITEMS items)

@@ -22,25 +22,6 @@ constexpr int CP_MAX_PARTS = 4;       // len(MLOParts)
 constexpr int CP_MAX_PART = 16;       // largest MLOParts value
 constexpr int CP_MAX_SEGMENTS = 1022; // + the tail segment = cpd_outline_dbscan's 1023 frames
 
-__device__ __forceinline__ uint32_t cp_fkey(float f) {        // order-preserving uint key of a float
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float cp_funkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ float cp_h(float v) { return (float)(_Float16)v; }   // round to float16 (nearest even)
-
-// row r of a [.][stride] float16 / float32 array as three floats (exact)
-__device__ __forceinline__ void cp_load(const void *p, int is_half, int stride, long long r, float &x, float &y, float &z) {
-    if (is_half) {
-        const _Float16 *q = static_cast<const _Float16 *>(p) + r * stride;
-        x = (float)q[0], y = (float)q[1], z = (float)q[2];
-    } else {
-        const float *q = static_cast<const float *>(p) + r * stride;
-        x = q[0], y = q[1], z = q[2];
-    }
-}
 __device__ __forceinline__ void cp_store3(void *p, int is_half, long long r, float x, float y, float z) {
     if (is_half) {
         _Float16 *q = static_cast<_Float16 *>(p) + r * 3;
@@ -49,15 +30,6 @@ __device__ __forceinline__ void cp_store3(void *p, int is_half, long long r, flo
         float *q = static_cast<float *>(p) + r * 3;
         q[0] = x, q[1] = y, q[2] = z;
     }
-}
-
-__device__ __forceinline__ int cp_seg_of(const int32_t *off, int n, int i) {   // largest s < n with off[s] <= i
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 __device__ __forceinline__ int cp_wave_sum(int v) {
@@ -136,7 +108,7 @@ struct CropTest {
     double bx, by, rad;
     __device__ __forceinline__ bool operator()(int i) const {
         float x, y, z;
-        cp_load(points, is_half, stride, base + i, x, y, z);
+        load_xyz(points, is_half, stride, base + i, x, y, z);
         const double dx = (double)x - bx, dy = (double)y - by;
         return sqrt(dx * dx + dy * dy) < rad;
     }
@@ -173,7 +145,7 @@ __global__ void __launch_bounds__(CP_THREADS) cp_crop_fill_kernel(CropArgs a) {
     cp_compact(n, sm4, false, t, [&](int i, int pos) {
         if (pos >= room) return;   // the offsets are this test's own counts: never taken
         float x, y, z;
-        cp_load(a.points, a.is_half, a.stride, t.base + i, x, y, z);
+        load_xyz(a.points, a.is_half, a.stride, t.base + i, x, y, z);
         cp_store3(a.out_rows, a.is_half, o0 + pos, x, y, z);
         a.out_src[o0 + pos] = i;
     });
@@ -203,21 +175,21 @@ __global__ void __launch_bounds__(CP_THREADS) cp_density_kernel(FilterArgs a) {
     __shared__ float tx[CP_THREADS], ty[CP_THREADS], tz[CP_THREADS];
     const int i = blockIdx.x * CP_THREADS + threadIdx.x;
     const int first = blockIdx.x * CP_THREADS, last = min(first + CP_THREADS, a.n_rows) - 1;
-    const int j0 = a.seg_off[cp_seg_of(a.seg_off, a.n_segments, first)];
-    const int j1 = a.seg_off[cp_seg_of(a.seg_off, a.n_segments, last) + 1];
+    const int j0 = a.seg_off[segment_of(a.seg_off, a.n_segments, first)];
+    const int j1 = a.seg_off[segment_of(a.seg_off, a.n_segments, last) + 1];
     int s0 = 0, s1 = 0;
     double x = 0.0, y = 0.0, z = 0.0;
     if (i < a.n_rows) {
-        const int s = cp_seg_of(a.seg_off, a.n_segments, i);
+        const int s = segment_of(a.seg_off, a.n_segments, i);
         s0 = a.seg_off[s], s1 = a.seg_off[s + 1];
         float fx, fy, fz;
-        cp_load(a.rows, a.is_half, 3, i, fx, fy, fz);
+        load_xyz(a.rows, a.is_half, 3, i, fx, fy, fz);
         x = fx, y = fy, z = fz;
     }
     int cnt = 0;
     for (int t0 = j0; t0 < j1; t0 += CP_THREADS) {
         const int j = t0 + threadIdx.x;
-        if (j < j1) cp_load(a.rows, a.is_half, 3, j, tx[threadIdx.x], ty[threadIdx.x], tz[threadIdx.x]);
+        if (j < j1) load_xyz(a.rows, a.is_half, 3, j, tx[threadIdx.x], ty[threadIdx.x], tz[threadIdx.x]);
         __syncthreads();
         const int k0 = max(t0, s0) - t0, k1 = min(min(t0 + CP_THREADS, j1), s1) - t0;
         for (int k = k0; k < k1; ++k) {
@@ -239,7 +211,7 @@ struct WindowTest {
     __device__ __forceinline__ bool operator()(int i) const {
         if (!mask[base + i]) return false;
         float x, y, z;
-        cp_load(rows, is_half, 3, base + i, x, y, z);
+        load_xyz(rows, is_half, 3, base + i, x, y, z);
         return z > thr && (double)z < z_max;
     }
 };
@@ -258,8 +230,8 @@ __global__ void __launch_bounds__(CP_THREADS) cp_zmin_kernel(FilterArgs a) {
     for (int i = threadIdx.x; i < n; i += CP_THREADS) {
         if (!a.mask[o0 + i]) continue;
         float x, y, z;
-        cp_load(a.rows, a.is_half, 3, o0 + i, x, y, z);
-        key = min(key, cp_fkey(z));
+        load_xyz(a.rows, a.is_half, 3, o0 + i, x, y, z);
+        key = min(key, float_key(z));
         ++kept;
     }
     if (kept) {
@@ -269,11 +241,11 @@ __global__ void __launch_bounds__(CP_THREADS) cp_zmin_kernel(FilterArgs a) {
     __syncthreads();
     const bool had = s_kept > 0;
     const double *b = a.boxes + (size_t)s * 7;
-    const float zf = had ? cp_funkey(s_key) : 0.0f;
+    const float zf = had ? float_unkey(s_key) : 0.0f;
     const double z_min = had ? (double)zf : b[2] - b[5] / 2;
     const double z_max = b[2] + b[5] / 2;
     // z_min + 0.2 as numpy 2 evaluates it: the Python float becomes the scalar's dtype, the sum is rounded to it
-    const float thr = a.is_half ? cp_h(zf + cp_h(0.2f)) : zf + 0.2f;
+    const float thr = a.is_half ? round_half(zf + round_half(0.2f)) : zf + 0.2f;
     if (threadIdx.x == 0) {
         double h = z_max - z_min;
         double zc = h / 2 + z_min;
@@ -281,7 +253,7 @@ __global__ void __launch_bounds__(CP_THREADS) cp_zmin_kernel(FilterArgs a) {
             // the reference assigns the Python float 1.3: with z_min a scalar of the frame's dtype, h/2 + z_min is then
             // the sum in that dtype (numpy 2); without dense rows z_min is a float64 and so is the sum
             h = 1.3;
-            zc = !had ? 1.3 / 2 + z_min : (double)(a.is_half ? cp_h(cp_h(0.65f) + zf) : 0.65f + zf);
+            zc = !had ? 1.3 / 2 + z_min : (double)(a.is_half ? round_half(round_half(0.65f) + zf) : 0.65f + zf);
         }
         double *nb = a.new_box + (size_t)s * 7;
         nb[0] = b[0], nb[1] = b[1], nb[2] = zc, nb[3] = b[3], nb[4] = b[4], nb[5] = h, nb[6] = b[6];
@@ -313,7 +285,7 @@ __global__ void __launch_bounds__(CP_THREADS) cp_window_fill_kernel(FilterArgs a
     cp_compact(a.had[s] ? n : 0, sm4, false, t, [&](int i, int pos) {
         if (pos >= room) return;
         float x, y, z;
-        cp_load(a.rows, a.is_half, 3, o0 + i, x, y, z);
+        load_xyz(a.rows, a.is_half, 3, o0 + i, x, y, z);
         cp_store3(a.filt_rows, a.is_half, f0 + pos, x, y, z);
         a.filt_src[f0 + pos] = a.crop_src[o0 + i];
     });
@@ -352,12 +324,12 @@ struct ScoreArgs {
 __global__ void __launch_bounds__(CP_THREADS) cp_cluster_stats_kernel(ScoreArgs a) {
     const int i = blockIdx.x * CP_THREADS + threadIdx.x;
     if (i >= a.n_rows) return;
-    const int s = cp_seg_of(a.off, a.n_segments + 1, i);
+    const int s = segment_of(a.off, a.n_segments + 1, i);
     if (s >= a.n_segments || i - a.off[s] >= a.count[s]) return;
     const int l = a.labels[i];
     if (l < 0 || l >= a.n_clusters[s] || a.off[s] + l >= a.off[s + 1]) return;
     atomicAdd(a.csize + a.off[s] + l, 1);
-    atomicMax(a.czmax + a.off[s] + l, cp_fkey(a.xyz[3 * (size_t)i + 2]));
+    atomicMax(a.czmax + a.off[s] + l, float_key(a.xyz[3 * (size_t)i + 2]));
 }
 
 // one workgroup per segment: the first valid cluster of strictly greatest size, then the cell counts of its rows
@@ -374,7 +346,7 @@ __global__ void __launch_bounds__(CP_THREADS) cp_best_occ_kernel(ScoreArgs a) {
         unsigned long long best = 0ull;
         for (int l = threadIdx.x; l < nc; l += CP_THREADS) {
             const int sz = a.csize[o0 + l];
-            if (sz > a.cluster_min_points && (double)cp_funkey(a.czmax[o0 + l]) < a.discard_max_height) {
+            if (sz > a.cluster_min_points && (double)float_unkey(a.czmax[o0 + l]) < a.discard_max_height) {
                 // greatest size first, lowest label among equals
                 const unsigned long long k = ((unsigned long long)(uint32_t)sz << 32) | (0xffffffffu - (uint32_t)l);
                 best = best > k ? best : k;
@@ -447,11 +419,6 @@ ScoreLayout score_layout(long long n_rows) {
     return L;
 }
 
-template <class T>
-T *at(void *ws, size_t off) {
-    return reinterpret_cast<T *>(static_cast<char *>(ws) + off);
-}
-
 int crop_args(CropArgs &a, const void *points, int is_half, int row_stride, const int32_t *frame_off, int n_frames,
               const double *boxes, const int32_t *seg_frame, int n_segments) {
     if (n_segments < 0 || n_segments > CP_MAX_SEGMENTS || n_frames <= 0 || row_stride < 3 || (is_half != 0 && is_half != 1))
@@ -520,7 +487,7 @@ int cpd_cproto_filter(const void *rows, int is_half, const int32_t *seg_off, con
     FilterArgs a;
     a.rows = rows, a.is_half = is_half, a.n_segments = n_segments, a.n_rows = n_rows, a.seg_off = seg_off;
     a.crop_src = crop_src, a.boxes = boxes, a.rad2 = radius * radius, a.mask = dens_mask, a.z_min = z_min;
-    a.new_box = new_box, a.had = had_points, a.thr = at<float>(workspace, L.thr), a.counts = at<int32_t>(workspace, L.counts);
+    a.new_box = new_box, a.had = had_points, a.thr = ws_at<float>(workspace, L.thr), a.counts = ws_at<int32_t>(workspace, L.counts);
     a.filt_off = filt_off, a.filt_rows = filt_rows, a.filt_src = filt_src;
     if (n_segments > 0 && n_rows > 0) cp_density_kernel<<<cpd_div_up(n_rows, CP_THREADS), CP_THREADS, 0, st>>>(a);
     if (n_segments > 0) cp_zmin_kernel<<<n_segments, CP_THREADS, 0, st>>>(a);
@@ -556,7 +523,7 @@ int cpd_cproto_score(const float *ng_xyz, const int32_t *ng_src, const int32_t *
     a.had = had_points, a.filt_src = filt_src, a.m = m, a.new_box = new_box, a.n_segments = n_segments, a.n_rows = n_rows;
     a.n_parts = n_parts, a.min_rows = min_rows, a.cluster_min_points = cluster_min_points, a.discard_max_height = discard_max_height;
     for (int p = 0; p < CP_MAX_PARTS; ++p) a.parts[p] = p < n_parts ? parts[p] : 1;
-    a.csize = at<int32_t>(workspace, L.csize), a.czmax = at<uint32_t>(workspace, L.czmax);
+    a.csize = ws_at<int32_t>(workspace, L.csize), a.czmax = ws_at<uint32_t>(workspace, L.czmax);
     a.occ = occ, a.best_label = best_label, a.best_count = best_count, a.out_off = out_off, a.out_xyz = out_xyz;
     a.out_src = out_src;
     CPD_HIP_TRY(hipMemsetAsync(workspace, 0, L.total, st));   // sizes 0, max z keys below every float

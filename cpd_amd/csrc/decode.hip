@@ -27,14 +27,6 @@ struct MapView {  // map[pixel * pix + channel * ch] of the sample the pointer w
     }
 };
 
-__device__ __forceinline__ uint32_t f2key(float f) {
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 struct TopkSmem {
@@ -178,7 +170,7 @@ __device__ bool block_topk_logits(const MapView &hm, int cls, int n, int K, Topk
         const float x = hm.at(i, cls);
         if (logit_bin(x) >= bstar) {
             const uint32_t pos = atomicAdd(&h.cnt, 1u);
-            sm.packed[pos] = ((unsigned long long)f2key(sigmoidf(x)) << 32) | (uint32_t)(~(uint32_t)i);
+            sm.packed[pos] = ((unsigned long long)float_key(sigmoidf(x)) << 32) | (uint32_t)(~(uint32_t)i);
         }
     }
     __syncthreads();
@@ -200,11 +192,11 @@ __device__ bool block_topk_logits(const MapView &hm, int cls, int n, int K, Topk
 struct SigKey {
     MapView hm;
     int cls;
-    __device__ __forceinline__ uint32_t operator()(int i) const { return f2key(sigmoidf(hm.at(i, cls))); }
+    __device__ __forceinline__ uint32_t operator()(int i) const { return float_key(sigmoidf(hm.at(i, cls))); }
 };
 struct ArrKey {
     const float *v;
-    __device__ __forceinline__ uint32_t operator()(int i) const { return f2key(v[i]); }
+    __device__ __forceinline__ uint32_t operator()(int i) const { return float_key(v[i]); }
 };
 
 __global__ void __launch_bounds__(1024) topk_class_kernel(MapView hm_all, long long sample_stride, int num_class, int hw,
@@ -217,7 +209,7 @@ __global__ void __launch_bounds__(1024) topk_class_kernel(MapView hm_all, long l
     const size_t o = ((size_t)b * num_class + cls) * K;
     for (int k = threadIdx.x; k < K; k += blockDim.x) {
         unsigned long long p = sm.packed[k];
-        s1[o + k] = key2f((uint32_t)(p >> 32));
+        s1[o + k] = float_unkey((uint32_t)(p >> 32));
         i1[o + k] = (int32_t)(~(uint32_t)p);
     }
 }
@@ -256,7 +248,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecodeParams q, const floa
         const int n = q.num_class * K;
         for (int i2 = threadIdx.x; i2 < n; i2 += blockDim.x) {
             const int c = i2 / K, j = i2 - c * K;
-            const uint32_t key = f2key(s1[i2]);
+            const uint32_t key = float_key(s1[i2]);
             int rank = j;
             for (int c2 = 0; c2 < q.num_class; ++c2) {
                 if (c2 == c) continue;
@@ -264,7 +256,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecodeParams q, const floa
                 int lo = 0, hi = K;
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
-                    const uint32_t km = f2key(l[mid]);
+                    const uint32_t km = float_key(l[mid]);
                     if (c2 < c ? km >= key : km > key) lo = mid + 1; else hi = mid;
                 }
                 rank += lo;
@@ -280,7 +272,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecodeParams q, const floa
     uint32_t keep = 0;
     if (k < K) {
         unsigned long long p = sm.packed[k];
-        sc = key2f((uint32_t)(p >> 32));
+        sc = float_unkey((uint32_t)(p >> 32));
         const int i2 = (int)(~(uint32_t)p);
         cls = i2 / K;
         const int ind = i1[i2];

@@ -27,11 +27,6 @@ constexpr int MF_HEAD_PARTS = 10;       // correct_heading's parts
 constexpr unsigned long long MF_EMPTY = ~0ull;
 constexpr int MF_CELL_BITS = 21;        // per axis: 2^21 cells of 0.1 m
 
-template <class T>
-T *at(void *ws, size_t off) {
-    return reinterpret_cast<T *>(static_cast<char *>(ws) + off);
-}
-
 // ---- 1. gather (mfcf.py:53-72) -------------------------------------------------------------------------------------------
 
 struct GatherKeep {                      // what the keep test reads
@@ -79,13 +74,6 @@ struct VoxelArgs {
     int32_t *out_off;            // [n_frames + 2]
 };
 
-__device__ __forceinline__ uint32_t mf_fkey(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float mf_funkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 // the frame whose slice holds row i (the last frame that starts at or before it), -1 past its count
 __device__ __forceinline__ int mf_frame_of(const VoxelArgs &a, int i) {
     int f = 0;
@@ -98,7 +86,7 @@ __global__ void __launch_bounds__(256) vs_min_kernel(VoxelArgs a) {
     const int f = i < a.n_points ? mf_frame_of(a, i) : -1;
     uint32_t k[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
     if (f >= 0)
-        for (int d = 0; d < 3; ++d) k[d] = mf_fkey(a.pts[3 * (size_t)i + d]);
+        for (int d = 0; d < 3; ++d) k[d] = float_key(a.pts[3 * (size_t)i + d]);
     // a wave of one frame reduces first (the common case); a wave that straddles frames sends every lane's keys
     const int f0 = __shfl(f, 0, 64);
     if (__all(f == f0 || f < 0)) {
@@ -122,15 +110,6 @@ __device__ __forceinline__ float mf_floor_divide(float a, float b) {
     return fl;
 }
 
-__device__ __forceinline__ unsigned long long mf_hash(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
 __global__ void __launch_bounds__(256) vs_insert_kernel(VoxelArgs a, float res) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_points) return;
@@ -143,7 +122,7 @@ __global__ void __launch_bounds__(256) vs_insert_kernel(VoxelArgs a, float res) 
     }
     unsigned long long key = 0;
     for (int d = 0; d < 3; ++d) {
-        const float c = mf_floor_divide(__fsub_rn(a.pts[3 * (size_t)i + d], mf_funkey(a.fmin[3 * f + d])), res);
+        const float c = mf_floor_divide(__fsub_rn(a.pts[3 * (size_t)i + d], float_unkey(a.fmin[3 * f + d])), res);
         if (!(c >= 0.0f && c < (float)(1 << MF_CELL_BITS))) {   // NaN, or a cloud wider than the key
             atomicOr(a.err, 1);
             return;
@@ -152,7 +131,7 @@ __global__ void __launch_bounds__(256) vs_insert_kernel(VoxelArgs a, float res) 
     }
     const unsigned long long base = 2ull * (unsigned long long)a.off[f];
     const unsigned long long size = 2ull * (unsigned long long)(a.off[f + 1] - a.off[f]);   // >= 2 slots per row: never full
-    unsigned long long s = mf_hash(key) % size;
+    unsigned long long s = mix64(key) % size;
     for (;;) {
         const unsigned long long prev = atomicCAS(a.keys + base + s, MF_EMPTY, key);
         if (prev == MF_EMPTY || prev == key) break;
@@ -175,19 +154,14 @@ struct VoxelLayout {
 };
 VoxelLayout vs_layout(int n_frames, long long n_points) {
     VoxelLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += cpd_align(bytes);
-        return at;
-    };
-    L.fmin = take((size_t)n_frames * 12);
-    L.keys = take((size_t)n_points * 16);
-    L.last = take((size_t)n_points * 8);
-    L.first = take((size_t)n_points * 8);
-    L.slot = take((size_t)n_points * 4);
-    L.scan = take((size_t)scan_num_blocks(n_points) * 4);
-    L.total = o;
+    Carve c;
+    L.fmin = c.take((size_t)n_frames * 12);
+    L.keys = c.take((size_t)n_points * 16);
+    L.last = c.take((size_t)n_points * 8);
+    L.first = c.take((size_t)n_points * 8);
+    L.slot = c.take((size_t)n_points * 4);
+    L.scan = c.take((size_t)scan_num_blocks(n_points) * 4);
+    L.total = c.o;
     return L;
 }
 
@@ -247,11 +221,11 @@ __global__ void __launch_bounds__(RF_THREADS) mf_dgd_kernel(DgdArgs a) {
     __syncthreads();
     uint32_t zk = 0xffffffffu;
     for (int i = threadIdx.x; i < c.n; i += RF_THREADS)
-        if (c.labels[i] == c.label) zk = min(zk, mf_fkey(c.xyz[3 * (size_t)i + 2]));
+        if (c.labels[i] == c.label) zk = min(zk, float_key(c.xyz[3 * (size_t)i + 2]));
     for (int s = 32; s; s >>= 1) zk = min(zk, (uint32_t)__shfl_xor((int)zk, s, 64));
     if ((threadIdx.x & 63) == 0) atomicMin(&szmin, zk);
     __syncthreads();
-    c.cut = szmin == 0xffffffffu ? INFINITY : (a.steps & 8) ? -INFINITY : (double)mf_funkey(szmin) + 0.2;
+    c.cut = szmin == 0xffffffffu ? INFINITY : (a.steps & 8) ? -INFINITY : (double)float_unkey(szmin) + 0.2;
     int cnt = 0;
     for (int i = threadIdx.x; i < c.n; i += RF_THREADS) {
         double x, y, z;
@@ -398,7 +372,7 @@ int cpd_mfcf_gather(const void *const *sweep_pts, const void *const *sweep_h, co
                 if (!v) return;
                 const int t = mf_segment(k, (int)i);
                 float x, y, z;
-                pp_load(r.pts[t], r.half[t], r.stride[t], (int)i - k.off[t], x, y, z);
+                load_xyz(r.pts[t], r.half[t], r.stride[t], (int)i - k.off[t], x, y, z);
                 if (t < k.n_win) {
                     float wx, wy, wz;
                     pp_rigid3(r.pose[t], x, y, z, wx, wy, wz);
@@ -428,8 +402,8 @@ int cpd_mfcf_voxel_sample(const float *points, const int32_t *frame_off, const i
     hipStream_t st = cpd_s(stream);
     VoxelArgs a;
     a.pts = points, a.off = frame_off, a.count = frame_count, a.n_frames = n_frames, a.n_points = n_points;
-    a.fmin = at<uint32_t>(workspace, L.fmin), a.keys = at<unsigned long long>(workspace, L.keys);
-    a.first = at<int32_t>(workspace, L.first), a.last = at<int32_t>(workspace, L.last), a.slot = at<int32_t>(workspace, L.slot);
+    a.fmin = ws_at<uint32_t>(workspace, L.fmin), a.keys = ws_at<unsigned long long>(workspace, L.keys);
+    a.first = ws_at<int32_t>(workspace, L.first), a.last = ws_at<int32_t>(workspace, L.last), a.slot = ws_at<int32_t>(workspace, L.slot);
     a.err = err, a.out = out, a.out_src = out_src, a.out_off = out_off;
     // fmin keys and table keys start at all ones; keys and last are adjacent (last = -1: below every row), first = 0x7f7f7f7f
     CPD_HIP_TRY(hipMemsetAsync(a.fmin, 0xff, L.first, st));
@@ -459,7 +433,7 @@ int cpd_mfcf_voxel_sample(const float *points, const int32_t *frame_off, const i
                 ac.out_src[pre] = src - ac.off[f];
             }
         },
-        at<uint32_t>(workspace, L.scan), out_off + n_frames, -1, st);
+        ws_at<uint32_t>(workspace, L.scan), out_off + n_frames, -1, st);
     if (rc != CPD_OK) return rc;
     vs_tail_kernel<<<cpd_div_up(n_frames + 1, 256), 256, 0, st>>>(a);
     return cpd_check_launch();

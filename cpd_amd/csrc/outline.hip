@@ -4,10 +4,10 @@
 //      (frame, segment) for the serial line fit in float64, per-point labelling over the +-7 neighbouring segment positions,
 //      distance bands, and a stable per-frame compaction into the canonical order (bands; high points in input order, then
 //      low non-ground points by segment, input order within a segment);
-//   2. cpd_outline_dbscan : sklearn DBSCAN(eps, min_samples) labels -- a hashed uniform grid of side eps, neighbour counts
-//      (float64 d^2 <= eps^2), union-find over core-core pairs that hooks the larger root under the smaller (the root of a
-//      component is its lowest index whatever the schedule), border label = lowest cluster among adjacent cores, cluster
-//      number = rank of the root;
+//   2. cpd_outline_dbscan : sklearn DBSCAN(eps, min_samples) labels -- the hashed uniform grid of hash_grid.h with side eps,
+//      neighbour counts (float64 d^2 <= eps^2), union-find over core-core pairs that hooks the larger root under the smaller
+//      (the root of a component is its lowest index whatever the schedule), border label = lowest cluster among adjacent
+//      cores, cluster number = rank of the root;
 //   3. cpd_outline_boxes : clustering's filter + box_fit -- low-point cut, 2-D convex hull by gift wrapping (one wave per
 //      cluster, exact float64 orientation tests), one lane per hull-edge angle for minimum_bounding_rectangle_distance's
 //      score, the box and box_fit's adjustments and filter.
@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "hash_grid.h"
 
 namespace {
 
@@ -26,25 +27,6 @@ constexpr int OL_SEARCH = 7;          // largest k with k * 2 pi / 150 < line_se
 constexpr int OL_MAX_BANDS = 6;
 constexpr int OL_NBUCKET = OL_MAX_BANDS * (OL_NSEG + 1);
 constexpr int OL_ORDER_THREADS = 512;
-constexpr unsigned long long OL_EMPTY = ~0ull;
-
-__device__ __forceinline__ uint32_t ol_fkey(float f) {        // order-preserving uint key of a float
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ol_funkey(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ float ol_h(float v) { return (float)(_Float16)v; }   // round to float16 (nearest even)
-
-__device__ __forceinline__ int ol_frame_of(const int32_t *off, int n_frames, int i) {
-    int lo = 0, hi = n_frames - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // ---- 1. ground removal ------------------------------------------------------------------------------------------------
 
@@ -70,32 +52,22 @@ struct GroundArgs {
     int32_t *out_src, *out_count;
 };
 
-__device__ __forceinline__ void ol_load(const GroundArgs &a, int i, float &x, float &y, float &z) {
-    if (a.is_half) {
-        const _Float16 *p = static_cast<const _Float16 *>(a.points) + (size_t)i * a.stride;
-        x = (float)p[0], y = (float)p[1], z = (float)p[2];
-    } else {
-        const float *p = static_cast<const float *>(a.points) + (size_t)i * a.stride;
-        x = p[0], y = p[1], z = p[2];
-    }
-}
-
 // Processor.project_5D + filter_out_range (ground_removal.py:124-159); the high / low split of remove_ground (outline_utils.py:544-546)
 __global__ void __launch_bounds__(256) ol_project_kernel(GroundArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_points) return;
     float x, y, z;
-    ol_load(a, i, x, y, z);
+    load_xyz(a.points, a.is_half, a.stride, i, x, y, z);
     if (z >= a.c_high) {   // ground_max_threshold
         a.code[i] = -2;
         return;
     }
     float q_seg, q_bin;
     if (a.is_half) {   // numpy float16 ufuncs: compute in float32, round to float16 after every op
-        const float ang = ol_h(atan2f(y, x));
-        q_seg = ol_h(ol_h(ang + a.c_pi) / a.c_seg_step);
-        const float r = ol_h(sqrtf(ol_h(ol_h(x * x) + ol_h(y * y))));
-        q_bin = ol_h(ol_h(r - a.c_rmin) / a.c_bin_step);
+        const float ang = round_half(atan2f(y, x));
+        q_seg = round_half(round_half(ang + a.c_pi) / a.c_seg_step);
+        const float r = round_half(sqrtf(round_half(round_half(x * x) + round_half(y * y))));
+        q_bin = round_half(round_half(r - a.c_rmin) / a.c_bin_step);
     } else {
         q_seg = (atan2f(y, x) + a.c_pi) / a.c_seg_step;
         q_bin = (sqrtf(x * x + y * y) - a.c_rmin) / a.c_bin_step;
@@ -112,8 +84,8 @@ __global__ void __launch_bounds__(256) ol_project_kernel(GroundArgs a) {
     }
     const int seg = (int)fs, bin = (int)fb;
     a.code[i] = seg * OL_NBIN + bin;
-    const int f = ol_frame_of(a.off, a.n_frames, i);
-    atomicMin(a.minz + (size_t)f * OL_NCELL + seg * OL_NBIN + bin, ol_fkey(z));
+    const int f = segment_of(a.off, a.n_frames, i);
+    atomicMin(a.minz + (size_t)f * OL_NCELL + seg * OL_NBIN + bin, float_key(z));
 }
 
 // least squares z = m * bin + b over runs[r0..r1] by running sums in list order (tests/ref_outline.py fit_line)
@@ -149,7 +121,7 @@ __global__ void __launch_bounds__(256) ol_fit_kernel(GroundArgs a) {
         for (int b = 0; b < OL_NBIN; ++b) {
             cov[b] = make_double2(__longlong_as_double(0x7ff8000000000000ll), 0.0);
             const uint32_t k = mz[seg * OL_NBIN + b];
-            if (k != 0xffffffffu) run[n++] = make_double2((double)b, (double)ol_funkey(k));
+            if (k != 0xffffffffu) run[n++] = make_double2((double)b, (double)float_unkey(k));
         }
     }
     uint32_t tot;
@@ -218,9 +190,9 @@ __global__ void __launch_bounds__(256) ol_label_kernel(GroundArgs a) {
     const int c = a.code[i];
     int bucket = -1;
     if (c != -1) {
-        const int f = ol_frame_of(a.off, a.n_frames, i);
+        const int f = segment_of(a.off, a.n_frames, i);
         float x, y, z;
-        ol_load(a, i, x, y, z);
+        load_xyz(a.points, a.is_half, a.stride, i, x, y, z);
         int cls = 0;
         bool keep = true;
         if (c >= 0) {
@@ -297,7 +269,7 @@ __global__ void __launch_bounds__(OL_ORDER_THREADS) ol_order_kernel(GroundArgs a
             int pos = run[b] + rank;
             for (int w2 = 0; w2 < w; ++w2) pos += wcnt[w2][b];
             float x, y, z;
-            ol_load(a, i, x, y, z);
+            load_xyz(a.points, a.is_half, a.stride, i, x, y, z);
             float *o = a.out_xyz + (size_t)(base + pos) * 3;
             o[0] = x, o[1] = y, o[2] = z;
             a.out_src[base + pos] = i - base;
@@ -321,23 +293,18 @@ struct GroundLayout {
 };
 GroundLayout ground_layout(int n_frames, long long n_points) {
     GroundLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += cpd_align(bytes);
-        return at;
-    };
-    L.minz = take((size_t)n_frames * OL_NCELL * 4);
-    L.bcount = take((size_t)n_frames * OL_NBUCKET * 4);
-    L.err = take(4);
-    L.code = take((size_t)n_points * 4);
-    L.cover = take((size_t)n_frames * OL_NCELL * 16);
-    L.runs = take((size_t)n_frames * OL_NCELL * 16);
-    L.seg_pos = take((size_t)n_frames * OL_NSEG * 4);
-    L.pos_seg = take((size_t)n_frames * OL_NSEG * 4);
-    L.n_pos = take((size_t)n_frames * 4);
-    L.bucket = take((size_t)n_points * 4);
-    L.total = o;
+    Carve c;
+    L.minz = c.take((size_t)n_frames * OL_NCELL * 4);
+    L.bcount = c.take((size_t)n_frames * OL_NBUCKET * 4);
+    L.err = c.take(4);
+    L.code = c.take((size_t)n_points * 4);
+    L.cover = c.take((size_t)n_frames * OL_NCELL * 16);
+    L.runs = c.take((size_t)n_frames * OL_NCELL * 16);
+    L.seg_pos = c.take((size_t)n_frames * OL_NSEG * 4);
+    L.pos_seg = c.take((size_t)n_frames * OL_NSEG * 4);
+    L.n_pos = c.take((size_t)n_frames * 4);
+    L.bucket = c.take((size_t)n_points * 4);
+    L.total = c.o;
     return L;
 }
 
@@ -347,12 +314,7 @@ struct DbArgs {
     const float *xyz;
     const int32_t *off, *count;
     int n_frames, n_points, min_samples;
-    double eps, eps2;
-    unsigned long long hmask;
-    unsigned long long *keys;   // [H]
-    int32_t *ccount, *cstart, *cursor;  // [H]
-    int32_t *cell;              // [n_points] slot
-    float4 *members;            // [n_points] (x, y, z, index bits) in cell order
+    HashGrid grid;              // side eps, tag = frame, members (x, y, z, index bits)
     int32_t *parent;            // [n_points]; -1 = not core (or padding)
     int32_t *gpre;              // [n_points + 1] exclusive prefix of root flags
     uint32_t *scan_ws;
@@ -360,92 +322,25 @@ struct DbArgs {
 };
 
 __device__ __forceinline__ bool db_valid(const DbArgs &a, int i, int &f) {
-    f = ol_frame_of(a.off, a.n_frames, i);
+    f = segment_of(a.off, a.n_frames, i);
     return i - a.off[f] < a.count[f];
 }
-__device__ __forceinline__ void db_cell(const DbArgs &a, float x, float y, float z, long long c[3]) {
-    c[0] = (long long)floor((double)x / a.eps);
-    c[1] = (long long)floor((double)y / a.eps);
-    c[2] = (long long)floor((double)z / a.eps);
-}
-// (frame, cx, cy, cz) with the cell coordinates taken modulo 2^18: cells that alias share a slot, which costs distance
-// tests but never a wrong answer (every candidate is checked by its distance)
-__device__ __forceinline__ unsigned long long db_key(int f, long long cx, long long cy, long long cz) {
-    const unsigned long long m = (1ull << 18) - 1;
-    return ((unsigned long long)f << 54) | (((unsigned long long)cx & m) << 36) | (((unsigned long long)cy & m) << 18) |
-           ((unsigned long long)cz & m);
-}
-__device__ __forceinline__ unsigned long long db_hash(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-__device__ __forceinline__ int db_find_slot(const DbArgs &a, unsigned long long key) {
-    unsigned long long s = db_hash(key) & a.hmask;
-    for (;;) {
-        const unsigned long long k = a.keys[s];
-        if (k == key) return (int)s;
-        if (k == OL_EMPTY) return -1;
-        s = (s + 1) & a.hmask;
+// the grid's source: the rows within their frame's count, tagged with the frame, w = the row's index bits
+struct DbSrc {
+    DbArgs a;
+    __device__ __forceinline__ bool operator()(int i, int &f, float &x, float &y, float &z, float &w) const {
+        if (!db_valid(a, i, f)) return false;
+        x = a.xyz[3 * (size_t)i], y = a.xyz[3 * (size_t)i + 1], z = a.xyz[3 * (size_t)i + 2];
+        w = __int_as_float(i);
+        return true;
     }
-}
-
-__global__ void __launch_bounds__(256) db_insert_kernel(DbArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_points) return;
-    int f;
-    if (!db_valid(a, i, f)) {
-        a.cell[i] = -1;
-        return;
-    }
-    long long c[3];
-    db_cell(a, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2], c);
-    const unsigned long long key = db_key(f, c[0], c[1], c[2]);
-    unsigned long long s = db_hash(key) & a.hmask;
-    for (;;) {   // the table holds >= 2 slots per point: a free slot always exists
-        const unsigned long long prev = atomicCAS(a.keys + s, OL_EMPTY, key);
-        if (prev == OL_EMPTY || prev == key) break;
-        s = (s + 1) & a.hmask;
-    }
-    a.cell[i] = (int)s;
-    atomicAdd(a.ccount + s, 1);
-}
-
-__global__ void __launch_bounds__(256) db_fill_kernel(DbArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_points) return;
-    const int s = a.cell[i];
-    if (s < 0) return;
-    const int pos = atomicAdd(a.cursor + s, 1);
-    a.members[pos] = make_float4(a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2], __int_as_float(i));
-}
-
-__device__ __forceinline__ bool db_near(const DbArgs &a, double x, double y, double z, float4 q) {
-    const double dx = x - (double)q.x, dy = y - (double)q.y, dz = z - (double)q.z;
-    return (dx * dx + dy * dy) + dz * dz <= a.eps2;
-}
+};
 
 // visit every point within eps of point i (itself included); fn(j, q) returns false to stop
 template <class Fn>
 __device__ __forceinline__ void db_for_neighbours(const DbArgs &a, int i, int f, Fn fn) {
-    const float px = a.xyz[3 * (size_t)i], py = a.xyz[3 * (size_t)i + 1], pz = a.xyz[3 * (size_t)i + 2];
-    const double x = px, y = py, z = pz;
-    long long c[3];
-    db_cell(a, px, py, pz, c);
-    for (int dx = -1; dx <= 1; ++dx)
-        for (int dy = -1; dy <= 1; ++dy)
-            for (int dz = -1; dz <= 1; ++dz) {
-                const int s = db_find_slot(a, db_key(f, c[0] + dx, c[1] + dy, c[2] + dz));
-                if (s < 0) continue;
-                const int e = a.cstart[s] + a.ccount[s];
-                for (int k = a.cstart[s]; k < e; ++k) {
-                    const float4 q = a.members[k];
-                    if (db_near(a, x, y, z, q) && !fn(__float_as_int(q.w), q)) return;
-                }
-            }
+    grid_for_near(a.grid, f, a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2],
+                  [&](float4 q) { return fn(__float_as_int(q.w), q); });
 }
 
 __global__ void __launch_bounds__(256) db_core_kernel(DbArgs a) {
@@ -487,7 +382,7 @@ __device__ __forceinline__ void db_union(int32_t *parent, int u, int v) {
 __global__ void __launch_bounds__(256) db_union_kernel(DbArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n_points || a.parent[i] < 0) return;
-    int f = ol_frame_of(a.off, a.n_frames, i);
+    int f = segment_of(a.off, a.n_frames, i);
     db_for_neighbours(a, i, f, [&](int j, float4) {
         if (j < i && __hip_atomic_load(a.parent + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) db_union(a.parent, i, j);
         return true;
@@ -526,30 +421,16 @@ __global__ void __launch_bounds__(256) db_label_kernel(DbArgs a) {
 }
 
 struct DbLayout {
-    size_t keys, ccount, cstart, cursor, cell, members, parent, gpre, scan, total;
-    unsigned long long hsize;
+    GridLayout grid;
+    size_t parent, gpre, total;
 };
 DbLayout db_layout(long long n_points) {
     DbLayout L;
-    unsigned long long h = 1024;
-    while (h < 2ull * (unsigned long long)n_points) h <<= 1;
-    L.hsize = h;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += cpd_align(bytes);
-        return at;
-    };
-    L.keys = take(h * 8);
-    L.ccount = take(h * 4);
-    L.cstart = take(h * 4);
-    L.cursor = take(h * 4);
-    L.cell = take((size_t)n_points * 4);
-    L.members = take((size_t)n_points * 16);
-    L.parent = take((size_t)n_points * 4);
-    L.gpre = take(((size_t)n_points + 1) * 4);
-    L.scan = take((size_t)scan_num_blocks((long long)(h > (unsigned long long)n_points ? h : n_points)) * 4);
-    L.total = o;
+    Carve c;
+    L.grid = grid_carve(c, n_points);   // its scan words serve the root scan over the n_points <= slots / 2 rows too
+    L.parent = c.take((size_t)n_points * 4);
+    L.gpre = c.take(((size_t)n_points + 1) * 4);
+    L.total = c.o;
     return L;
 }
 
@@ -573,7 +454,7 @@ struct BoxArgs {
 };
 
 __device__ __forceinline__ bool bx_slot(const BoxArgs &a, int i, int &slot) {
-    const int f = ol_frame_of(a.off, a.n_frames, i);
+    const int f = segment_of(a.off, a.n_frames, i);
     if (i - a.off[f] >= a.count[f]) return false;
     const int l = a.labels[i];
     if (l < 0 || l >= a.n_clusters[f]) return false;
@@ -588,8 +469,8 @@ __global__ void __launch_bounds__(256) bx_stats_kernel(BoxArgs a) {
     if (!bx_slot(a, i, s)) return;
     const float z = a.xyz[3 * (size_t)i + 2];
     atomicAdd(a.csize + s, 1);
-    atomicMax(a.czmax + s, ol_fkey(z));
-    atomicMin(a.czmin + s, ol_fkey(z));
+    atomicMax(a.czmax + s, float_key(z));
+    atomicMin(a.czmin + s, float_key(z));
 }
 
 __global__ void __launch_bounds__(256) bx_fill_kernel(BoxArgs a) {
@@ -603,7 +484,7 @@ __global__ void __launch_bounds__(256) bx_fill_kernel(BoxArgs a) {
 __device__ __forceinline__ bool bx_kept(const BoxArgs &a, int s) {
     if (a.csize[s] == 0) return false;
     if (!a.apply_filter) return true;
-    return a.csize[s] > a.cluster_min_points && (double)ol_funkey(a.czmax[s]) < a.discard_max_height;
+    return a.csize[s] > a.cluster_min_points && (double)float_unkey(a.czmax[s]) < a.discard_max_height;
 }
 
 // r better than q as the next counter-clockwise hull vertex after p (every point lies left of p -> best, or on it nearer)
@@ -646,7 +527,7 @@ __global__ void __launch_bounds__(256) bx_fit_kernel(BoxArgs a) {
     for (int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); k < K; k += nwaves) {
         const int s = a.kept[k];
         const int m0 = a.cstart[s], mn = a.csize[s];
-        const double cut = (double)ol_funkey(a.czmin[s]) + 0.2;
+        const double cut = (double)float_unkey(a.czmin[s]) + 0.2;
         // pass 1: filtered count, z range, start vertex = lexicographic min of (y, x)
         int cnt = 0;
         double zlo = INFINITY, zhi = -INFINITY, sx = INFINITY, sy = INFINITY;
@@ -794,31 +675,21 @@ struct BoxLayout {
 };
 BoxLayout bx_layout(int n_frames, long long n_points) {
     BoxLayout L;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += cpd_align(bytes);
-        return at;
-    };
-    L.csize = take((size_t)n_points * 4);
-    L.czmax = take((size_t)n_points * 4);
-    L.n_kept = take(4);
-    L.fcount = take((size_t)n_frames * 4);
-    L.czmin = take((size_t)n_points * 4);
-    L.cstart = take((size_t)n_points * 4);
-    L.cursor = take((size_t)n_points * 4);
-    L.members = take((size_t)n_points * 4);
-    L.hull = take((size_t)n_points * 16);
-    L.kept = take((size_t)n_points * 4);
-    L.kbox = take((size_t)n_points * 64);
-    L.scan = take((size_t)scan_num_blocks(n_points) * 4);
-    L.total = o;
+    Carve c;
+    L.csize = c.take((size_t)n_points * 4);
+    L.czmax = c.take((size_t)n_points * 4);
+    L.n_kept = c.take(4);
+    L.fcount = c.take((size_t)n_frames * 4);
+    L.czmin = c.take((size_t)n_points * 4);
+    L.cstart = c.take((size_t)n_points * 4);
+    L.cursor = c.take((size_t)n_points * 4);
+    L.members = c.take((size_t)n_points * 4);
+    L.hull = c.take((size_t)n_points * 16);
+    L.kept = c.take((size_t)n_points * 4);
+    L.kbox = c.take((size_t)n_points * 64);
+    L.scan = c.take((size_t)scan_num_blocks(n_points) * 4);
+    L.total = c.o;
     return L;
-}
-
-template <class T>
-T *at(void *ws, size_t off) {
-    return reinterpret_cast<T *>(static_cast<char *>(ws) + off);
 }
 
 }  // namespace
@@ -848,11 +719,11 @@ int cpd_outline_ground(const void *points, int is_half, int row_stride, const in
     a.sensor_height = sensor_height, a.n_bands = n_bands;
     for (int i = 0; i < OL_MAX_BANDS; ++i) a.thr[i] = i < n_bands ? thr[i] : 0.0;
     for (int i = 0; i <= OL_MAX_BANDS; ++i) a.dist[i] = dist[i];
-    a.code = at<int32_t>(workspace, L.code), a.minz = at<uint32_t>(workspace, L.minz);
-    a.cover = at<double2>(workspace, L.cover), a.runs = at<double2>(workspace, L.runs);
-    a.seg_pos = at<int32_t>(workspace, L.seg_pos), a.pos_seg = at<int32_t>(workspace, L.pos_seg);
-    a.n_pos = at<int32_t>(workspace, L.n_pos), a.bucket = at<int32_t>(workspace, L.bucket);
-    a.bcount = at<int32_t>(workspace, L.bcount), a.err = err;
+    a.code = ws_at<int32_t>(workspace, L.code), a.minz = ws_at<uint32_t>(workspace, L.minz);
+    a.cover = ws_at<double2>(workspace, L.cover), a.runs = ws_at<double2>(workspace, L.runs);
+    a.seg_pos = ws_at<int32_t>(workspace, L.seg_pos), a.pos_seg = ws_at<int32_t>(workspace, L.pos_seg);
+    a.n_pos = ws_at<int32_t>(workspace, L.n_pos), a.bucket = ws_at<int32_t>(workspace, L.bucket);
+    a.bcount = ws_at<int32_t>(workspace, L.bcount), a.err = err;
     a.out_xyz = out_xyz, a.out_src = out_src, a.out_count = out_count;
     CPD_HIP_TRY(hipMemsetAsync(a.minz, 0xff, (size_t)n_frames * OL_NCELL * 4, st));
     CPD_HIP_TRY(hipMemsetAsync(a.bcount, 0, (size_t)n_frames * OL_NBUCKET * 4, st));
@@ -880,30 +751,14 @@ int cpd_outline_dbscan(const float *xyz, const int32_t *frame_off, const int32_t
     hipStream_t st = cpd_s(stream);
     DbArgs a;
     a.xyz = xyz, a.off = frame_off, a.count = frame_count, a.n_frames = n_frames, a.n_points = n_points;
-    a.min_samples = min_samples, a.eps = eps, a.eps2 = eps * eps, a.hmask = L.hsize - 1;
-    a.keys = at<unsigned long long>(workspace, L.keys), a.ccount = at<int32_t>(workspace, L.ccount);
-    a.cstart = at<int32_t>(workspace, L.cstart), a.cursor = at<int32_t>(workspace, L.cursor);
-    a.cell = at<int32_t>(workspace, L.cell), a.members = at<float4>(workspace, L.members);
-    a.parent = at<int32_t>(workspace, L.parent), a.gpre = at<int32_t>(workspace, L.gpre);
-    a.scan_ws = at<uint32_t>(workspace, L.scan), a.labels = labels, a.n_clusters = n_clusters;
-    CPD_HIP_TRY(hipMemsetAsync(a.keys, 0xff, L.hsize * 8, st));
-    CPD_HIP_TRY(hipMemsetAsync(a.ccount, 0, L.hsize * 4, st));
-    if (n_points == 0) {
-        CPD_HIP_TRY(hipMemsetAsync(n_clusters, 0, (size_t)n_frames * 4, st));
-        return CPD_OK;
-    }
+    a.min_samples = min_samples, a.grid = L.grid.view(workspace, eps, eps * eps);
+    a.parent = ws_at<int32_t>(workspace, L.parent), a.gpre = ws_at<int32_t>(workspace, L.gpre);
+    a.scan_ws = ws_at<uint32_t>(workspace, L.grid.scan), a.labels = labels, a.n_clusters = n_clusters;
     // frames with no rows still need n_clusters = 0 (the labelling kernel writes it from a frame's first row)
     CPD_HIP_TRY(hipMemsetAsync(n_clusters, 0, (size_t)n_frames * 4, st));
+    int rc = grid_build(a.grid, n_points, DbSrc{a}, a.scan_ws, st);
+    if (rc != CPD_OK || n_points == 0) return rc;
     const unsigned blocks = (unsigned)cpd_div_up(n_points, 256);
-    db_insert_kernel<<<blocks, 256, 0, st>>>(a);
-    int32_t *cstart = a.cstart, *cursor = a.cursor;
-    const int32_t *ccount = a.ccount;
-    int rc = device_scan(
-        (long long)L.hsize, [=] __device__(long long i) { return (uint32_t)ccount[i]; },
-        [=] __device__(long long i, uint32_t, uint32_t pre) { cstart[i] = (int32_t)pre, cursor[i] = (int32_t)pre; }, a.scan_ws,
-        nullptr, -1, st);
-    if (rc != CPD_OK) return rc;
-    db_fill_kernel<<<blocks, 256, 0, st>>>(a);
     db_core_kernel<<<blocks, 256, 0, st>>>(a);
     db_union_kernel<<<blocks, 256, 0, st>>>(a);
     db_root_kernel<<<blocks, 256, 0, st>>>(a);
@@ -937,12 +792,12 @@ int cpd_outline_boxes(const float *xyz, const int32_t *frame_off, const int32_t 
     a.cluster_min_points = (int)params[0], a.discard_max_height = params[1], a.min_box_volume = params[2];
     a.min_box_height = params[3], a.max_box_volume = params[4], a.max_box_len = params[5], a.thr0 = params[6];
     a.dist1 = params[7];
-    a.csize = at<int32_t>(workspace, L.csize), a.cstart = at<int32_t>(workspace, L.cstart);
-    a.cursor = at<int32_t>(workspace, L.cursor), a.czmax = at<uint32_t>(workspace, L.czmax);
-    a.czmin = at<uint32_t>(workspace, L.czmin), a.members = at<int32_t>(workspace, L.members);
-    a.hull = at<double2>(workspace, L.hull), a.kept = at<int32_t>(workspace, L.kept), a.n_kept = at<int32_t>(workspace, L.n_kept);
-    a.fcount = at<int32_t>(workspace, L.fcount);
-    a.kbox = at<double>(workspace, L.kbox), a.scan_ws = at<uint32_t>(workspace, L.scan), a.out = out;
+    a.csize = ws_at<int32_t>(workspace, L.csize), a.cstart = ws_at<int32_t>(workspace, L.cstart);
+    a.cursor = ws_at<int32_t>(workspace, L.cursor), a.czmax = ws_at<uint32_t>(workspace, L.czmax);
+    a.czmin = ws_at<uint32_t>(workspace, L.czmin), a.members = ws_at<int32_t>(workspace, L.members);
+    a.hull = ws_at<double2>(workspace, L.hull), a.kept = ws_at<int32_t>(workspace, L.kept), a.n_kept = ws_at<int32_t>(workspace, L.n_kept);
+    a.fcount = ws_at<int32_t>(workspace, L.fcount);
+    a.kbox = ws_at<double>(workspace, L.kbox), a.scan_ws = ws_at<uint32_t>(workspace, L.scan), a.out = out;
     // csize, czmax (key 0 = below every float), n_kept and fcount are adjacent: one clear; czmin keys start at all ones
     CPD_HIP_TRY(hipMemsetAsync(a.csize, 0, L.czmin, st));
     CPD_HIP_TRY(hipMemsetAsync(a.czmin, 0xff, (size_t)n_points * 4, st));
@@ -979,7 +834,7 @@ int cpd_outline_boxes(const float *xyz, const int32_t *frame_off, const int32_t 
         [=] __device__(long long k, uint32_t v, uint32_t pre) {
             if (!v) return;
             const int s = kept[k];
-            const int f = ol_frame_of(off, nf, s);
+            const int f = segment_of(off, nf, s);
             atomicAdd(fcount + f, 1);
             if ((int)pre < cap) {
                 double *o = out + nf + (size_t)pre * 8;

@@ -3,9 +3,9 @@
 //   a. every traversal point goes sweep -> world (its own pose) -> current frame (inverse of the current pose): two float64
 //      products in the accumulation order of the reference's np.mat product (pp_row below), each rounded to float32 (the
 //      rounding in world coordinates is the reference's and is kept);
-//   b. one hashed uniform grid of side r over all traversals, key (traversal, cx, cy, cz) with floor((double)coord / r) cell
-//      coordinates taken modulo 2^18: count per slot, prefix, fill float4 members in cell order (as outline.hip's DBSCAN grid);
-//   c. one lane per (query point, traversal) walks the 27 cells and counts the members with float64
+//   b. one hashed uniform grid of side r over all traversals, tagged by traversal (hash_grid.h, shared with outline.hip's
+//      DBSCAN);
+//   c. one lane per (query point, traversal) walks the 27 cells (grid_for_near) and counts the members with float64
 //      (dx*dx + dy*dy) + dz*dz <= r*r (cKDTree.query_ball_point(..., return_length=True): inclusive); lanes of a wave are
 //      consecutive query rows of one traversal, which in scan order walk the same cells. Queries are the RAW rows of the
 //      current frame, not transformed (that is what the reference does);
@@ -17,12 +17,12 @@
 #include <math.h>
 
 #include "common.h"
-#include "rigid_f64.h"   // pp_load, pp_row, pp_rigid3: shared with mfcf.hip
+#include "hash_grid.h"
+#include "rigid_f64.h"   // pp_row, pp_rigid3: shared with mfcf.hip
 
 namespace {
 
 constexpr int PP_MAX_TRAV = 16;
-constexpr unsigned long long PP_EMPTY = ~0ull;
 
 struct PpArgs {
     const void *query, *ref;
@@ -32,13 +32,8 @@ struct PpArgs {
     int32_t off[PP_MAX_TRAV + 1];
     double pose[PP_MAX_TRAV][12];   // rows 0..2 of the 4x4 sweep -> world matrices
     double cur_inv[12];             // rows 0..2 of inverse(current pose)
-    double r, r2, log_t;
-    unsigned long long hmask;
-    unsigned long long *keys;       // [H]
-    int32_t *ccount;                // [H]
-    int2 *range;                    // [H] (first member, cursor); the cursor is the end of the cell once the fill has run
-    int32_t *cell;                  // [n_ref] slot
-    float4 *members;                // [n_ref] (x, y, z, 0) in cell order
+    double log_t;
+    HashGrid grid;                  // side r over all traversals, tag = traversal, members (x, y, z, 0)
     int32_t *counts;                // [n_query][n_trav]
     uint16_t *h;                    // [n_query] float16 bits
 };
@@ -47,7 +42,7 @@ struct PpArgs {
 __device__ __forceinline__ int pp_ref_point(const PpArgs &a, int i, float &x, float &y, float &z) {
     int t = 0;
     while (t + 1 < a.n_trav && i >= a.off[t + 1]) ++t;
-    pp_load(a.ref, a.ref_half, a.ref_stride, i, x, y, z);
+    load_xyz(a.ref, a.ref_half, a.ref_stride, i, x, y, z);
     if (a.has_pose) {
         float wx, wy, wz;
         pp_rigid3(a.pose[t], x, y, z, wx, wy, wz);
@@ -56,53 +51,15 @@ __device__ __forceinline__ int pp_ref_point(const PpArgs &a, int i, float &x, fl
     return t;
 }
 
-__device__ __forceinline__ void pp_cell(const PpArgs &a, float x, float y, float z, long long c[3]) {
-    c[0] = (long long)floor((double)x / a.r);
-    c[1] = (long long)floor((double)y / a.r);
-    c[2] = (long long)floor((double)z / a.r);
-}
-// cells that alias modulo 2^18 share a slot: that costs distance tests, never a wrong count (every candidate is decided by
-// its distance, and the 27 keys of one query stay distinct). t <= 15, so no key equals PP_EMPTY.
-__device__ __forceinline__ unsigned long long pp_key(int t, long long cx, long long cy, long long cz) {
-    const unsigned long long m = (1ull << 18) - 1;
-    return ((unsigned long long)t << 54) | (((unsigned long long)cx & m) << 36) | (((unsigned long long)cy & m) << 18) |
-           ((unsigned long long)cz & m);
-}
-__device__ __forceinline__ unsigned long long pp_hash(unsigned long long k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return k;
-}
-
-__global__ void __launch_bounds__(256) pp_insert_kernel(PpArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_ref) return;
-    float x, y, z;
-    const int t = pp_ref_point(a, i, x, y, z);
-    long long c[3];
-    pp_cell(a, x, y, z, c);
-    const unsigned long long key = pp_key(t, c[0], c[1], c[2]);
-    unsigned long long s = pp_hash(key) & a.hmask;
-    for (;;) {   // the table holds >= 2 slots per point: a free slot always exists
-        const unsigned long long prev = atomicCAS(a.keys + s, PP_EMPTY, key);
-        if (prev == PP_EMPTY || prev == key) break;
-        s = (s + 1) & a.hmask;
+// the grid's source: every traversal point, tagged with its traversal
+struct PpSrc {
+    PpArgs a;
+    __device__ __forceinline__ bool operator()(int i, int &tag, float &x, float &y, float &z, float &w) const {
+        tag = pp_ref_point(a, i, x, y, z);
+        w = 0.f;
+        return true;
     }
-    a.cell[i] = (int)s;
-    atomicAdd(a.ccount + s, 1);
-}
-
-__global__ void __launch_bounds__(256) pp_fill_kernel(PpArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.n_ref) return;
-    float x, y, z;
-    pp_ref_point(a, i, x, y, z);
-    const int pos = atomicAdd(&a.range[a.cell[i]].y, 1);
-    a.members[pos] = make_float4(x, y, z, 0.f);
-}
+};
 
 __global__ void __launch_bounds__(256) pp_count_kernel(PpArgs a) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -110,26 +67,12 @@ __global__ void __launch_bounds__(256) pp_count_kernel(PpArgs a) {
     if (q >= a.n_query) return;
     int n = 0;
     if (a.off[t + 1] > a.off[t]) {
-        float fx, fy, fz;
-        pp_load(a.query, a.query_half, a.query_stride, q, fx, fy, fz);
-        const double x = fx, y = fy, z = fz;
-        long long c[3];
-        pp_cell(a, fx, fy, fz, c);
-        for (int dx = -1; dx <= 1; ++dx)
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dz = -1; dz <= 1; ++dz) {
-                    const unsigned long long key = pp_key(t, c[0] + dx, c[1] + dy, c[2] + dz);
-                    unsigned long long s = pp_hash(key) & a.hmask;
-                    unsigned long long k;
-                    while ((k = a.keys[s]) != key && k != PP_EMPTY) s = (s + 1) & a.hmask;
-                    if (k != key) continue;
-                    const int2 rg = a.range[s];
-                    for (int m = rg.x; m < rg.y; ++m) {
-                        const float4 p = a.members[m];
-                        const double ex = x - (double)p.x, ey = y - (double)p.y, ez = z - (double)p.z;
-                        n += ((ex * ex + ey * ey) + ez * ez <= a.r2) ? 1 : 0;
-                    }
-                }
+        float x, y, z;
+        load_xyz(a.query, a.query_half, a.query_stride, q, x, y, z);
+        grid_for_near(a.grid, t, x, y, z, [&](float4) {
+            ++n;
+            return true;
+        });
     }
     a.counts[(size_t)q * a.n_trav + t] = n;
 }
@@ -171,34 +114,16 @@ __global__ void __launch_bounds__(256) pp_score_kernel(PpArgs a) {
 }
 
 struct PpLayout {
-    size_t keys, ccount, range, cell, members, counts, scan, total;
-    unsigned long long hsize;
+    GridLayout grid;
+    size_t counts, total;
 };
 PpLayout pp_layout(long long n_query, long long n_ref, int n_trav) {
     PpLayout L;
-    unsigned long long h = 1024;
-    while (h < 2ull * (unsigned long long)n_ref) h <<= 1;
-    L.hsize = h;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += cpd_align(bytes);
-        return at;
-    };
-    L.keys = take(h * 8);
-    L.ccount = take(h * 4);
-    L.range = take(h * 8);
-    L.cell = take((size_t)n_ref * 4);
-    L.members = take((size_t)n_ref * 16);
-    L.counts = take((size_t)n_query * (size_t)(n_trav > 0 ? n_trav : 1) * 4);
-    L.scan = take((size_t)scan_num_blocks((long long)h) * 4);
-    L.total = o;
+    Carve c;
+    L.grid = grid_carve(c, n_ref);
+    L.counts = c.take((size_t)n_query * (size_t)(n_trav > 0 ? n_trav : 1) * 4);
+    L.total = c.o;
     return L;
-}
-
-template <class T>
-T *at(void *ws, size_t off) {
-    return reinterpret_cast<T *>(static_cast<char *>(ws) + off);
 }
 
 }  // namespace
@@ -232,28 +157,14 @@ int cpd_ppscore(const void *query, int n_query, int query_stride, int query_dtyp
     for (int t = 0; t < PP_MAX_TRAV; ++t)
         for (int k = 0; k < 12; ++k) a.pose[t][k] = (poses && t < n_trav) ? poses[(size_t)t * 16 + k] : 0.0;
     for (int k = 0; k < 12; ++k) a.cur_inv[k] = cur_pose_inv ? cur_pose_inv[k] : 0.0;
-    a.r = radius, a.r2 = radius * radius, a.log_t = log((double)(n_trav > 0 ? n_trav : 1)), a.hmask = L.hsize - 1;
-    a.keys = at<unsigned long long>(workspace, L.keys), a.ccount = at<int32_t>(workspace, L.ccount);
-    a.range = at<int2>(workspace, L.range), a.cell = at<int32_t>(workspace, L.cell);
-    a.members = at<float4>(workspace, L.members);
-    a.counts = counts ? counts : at<int32_t>(workspace, L.counts);
+    a.log_t = log((double)(n_trav > 0 ? n_trav : 1));
+    a.grid = L.grid.view(workspace, radius, radius * radius);
+    a.counts = counts ? counts : ws_at<int32_t>(workspace, L.counts);
     a.h = h;
     if (n_query == 0 || (n_trav == 0 && !h)) return CPD_OK;
     if (n_trav > 0) {
-        CPD_HIP_TRY(hipMemsetAsync(a.keys, 0xff, L.hsize * 8, st));
-        if (n_ref > 0) {
-            CPD_HIP_TRY(hipMemsetAsync(a.ccount, 0, L.hsize * 4, st));
-            const unsigned blocks = (unsigned)cpd_div_up(n_ref, 256);
-            pp_insert_kernel<<<blocks, 256, 0, st>>>(a);
-            int2 *range = a.range;
-            const int32_t *ccount = a.ccount;
-            const int rc = device_scan(
-                (long long)L.hsize, [=] __device__(long long i) { return (uint32_t)ccount[i]; },
-                [=] __device__(long long i, uint32_t, uint32_t pre) { range[i] = make_int2((int)pre, (int)pre); },
-                at<uint32_t>(workspace, L.scan), nullptr, -1, st);
-            if (rc != CPD_OK) return rc;
-            pp_fill_kernel<<<blocks, 256, 0, st>>>(a);
-        }
+        const int rc = grid_build(a.grid, n_ref, PpSrc{a}, ws_at<uint32_t>(workspace, L.grid.scan), st);
+        if (rc != CPD_OK) return rc;
         pp_count_kernel<<<dim3((unsigned)cpd_div_up(n_query, 256), (unsigned)n_trav), 256, 0, st>>>(a);
     }
     if (h) pp_score_kernel<<<(unsigned)cpd_div_up(n_query, 256), 256, 0, st>>>(a);

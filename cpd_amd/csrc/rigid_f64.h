@@ -1,20 +1,10 @@
-// rigid_f64.h -- one row load and the float64 pose product of points_rigid_transform (precompute_ppscore.py:36-45,
+// rigid_f64.h -- the float64 pose product of points_rigid_transform (precompute_ppscore.py:36-45,
 // outline_utils.py:328-338), shared by ppscore.hip and mfcf.hip. Both files are built with -ffp-contract=off; the only fused
 // multiply-adds are the explicit ones below, which are the reference's.
 #pragma once
 #include "common.h"
 
 namespace {
-
-__device__ __forceinline__ void pp_load(const void *base, int is_half, int stride, int i, float &x, float &y, float &z) {
-    if (is_half) {
-        const _Float16 *p = static_cast<const _Float16 *>(base) + (size_t)i * stride;
-        x = (float)p[0], y = (float)p[1], z = (float)p[2];
-    } else {
-        const float *p = static_cast<const float *>(base) + (size_t)i * stride;
-        x = p[0], y = p[1], z = p[2];
-    }
-}
 
 // One points_rigid_transform product (l.36-45): the np.mat product is a dgemm whose inner loop accumulates over k with fused
 // multiply-adds, acc = m0*x; acc = fma(m1, y, acc); acc = fma(m2, z, acc); acc + m3 (the last step multiplies by the exact 1

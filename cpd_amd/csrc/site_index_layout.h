@@ -18,21 +18,15 @@ struct IndexView {
 
 static IndexView index_carve(void *mem, int batch, const int32_t shape[3], int n_cap) {
     IndexView v;
-    size_t off = 0;
-    char *b = (char *)mem;
-    auto take = [&](size_t bytes) {
-        void *p = b ? (void *)(b + off) : nullptr;
-        off += cpd_align(bytes);
-        return p;
-    };
+    Carve c;
     v.cells = (long long)batch * shape[0] * shape[1] * shape[2];
     v.words = (v.cells + 63) / 64;
-    v.flags = (int32_t *)take(256);
-    v.bitmap = (uint64_t *)take((size_t)v.words * 8);
-    v.base = (uint32_t *)take((size_t)v.words * 4);
-    v.bsum = (uint32_t *)take((size_t)scan_num_blocks(v.words) * 4);
-    v.perm = (int32_t *)take((size_t)(n_cap > 0 ? n_cap : 1) * 4);
-    v.bytes = off;
+    v.flags = ws_at<int32_t>(mem, c.take(256));
+    v.bitmap = ws_at<uint64_t>(mem, c.take((size_t)v.words * 8));
+    v.base = ws_at<uint32_t>(mem, c.take((size_t)v.words * 4));
+    v.bsum = ws_at<uint32_t>(mem, c.take((size_t)scan_num_blocks(v.words) * 4));
+    v.perm = ws_at<int32_t>(mem, c.take((size_t)(n_cap > 0 ? n_cap : 1) * 4));
+    v.bytes = c.o;
     return v;
 }
 

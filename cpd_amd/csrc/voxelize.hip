@@ -91,27 +91,21 @@ struct VoxWs {
 
 static VoxWs carve(void *ws, int n, int P, int cap, long long cells) {
     VoxWs w;
-    size_t off = 0;
-    char *b = (char *)ws;
-    auto take = [&](size_t bytes) {
-        void *p = b ? (void *)(b + off) : nullptr;
-        off += cpd_align(bytes);
-        return p;
-    };
+    Carve c;
     w.words = (cells + 63) / 64;
-    w.bitmap = (uint64_t *)take((size_t)w.words * 8);
-    w.base = (uint32_t *)take((size_t)w.words * 4);
-    w.bsum_bm = (uint32_t *)take((size_t)scan_num_blocks(w.words) * 4);
-    w.bsum_pt = (uint32_t *)take((size_t)scan_num_blocks(n) * 4);
+    w.bitmap = ws_at<uint64_t>(ws, c.take((size_t)w.words * 8));
+    w.base = ws_at<uint32_t>(ws, c.take((size_t)w.words * 4));
+    w.bsum_bm = ws_at<uint32_t>(ws, c.take((size_t)scan_num_blocks(w.words) * 4));
+    w.bsum_pt = ws_at<uint32_t>(ws, c.take((size_t)scan_num_blocks(n) * 4));
     size_t nn = (size_t)(n > 0 ? n : 1);
-    w.pkey = (int32_t *)take(nn * 4);
-    w.prank = (int32_t *)take(nn * 4);
-    w.first = (int32_t *)take(nn * 4);
-    w.vid = (int32_t *)take(nn * 4);
-    w.slots = (int32_t *)take((size_t)(cap > 0 ? cap : 1) * P * 4);
-    w.counts = (int32_t *)take((size_t)(cap > 0 ? cap : 1) * 4);
-    w.nocc = (int32_t *)take(4);
-    w.bytes = off;
+    w.pkey = ws_at<int32_t>(ws, c.take(nn * 4));
+    w.prank = ws_at<int32_t>(ws, c.take(nn * 4));
+    w.first = ws_at<int32_t>(ws, c.take(nn * 4));
+    w.vid = ws_at<int32_t>(ws, c.take(nn * 4));
+    w.slots = ws_at<int32_t>(ws, c.take((size_t)(cap > 0 ? cap : 1) * P * 4));
+    w.counts = ws_at<int32_t>(ws, c.take((size_t)(cap > 0 ? cap : 1) * 4));
+    w.nocc = ws_at<int32_t>(ws, c.take(4));
+    w.bytes = c.o;
     return w;
 }
 

@@ -20,7 +20,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import outline
-from .outline import DBSCAN_GENERATOR_CONFIG, _get, _has, _paths
+from .outline import DBSCAN_GENERATOR_CONFIG, _get, _paths
+from .seq_io import SweepCache, dispatch_outline_box, frame_path, gpu_modules, run_sequences
 from .tracker import TrackSmooth
 
 # GeneratorConfig of tools/cfgs/dataset_configs/waymo_unsupervised/waymo_unsupervised_cproto.yaml: the aggregation, the
@@ -35,12 +36,6 @@ MFCF_CONFIG = dict(InitLabelGenerator='MFCF', GeneratorConfig=MFCF_GENERATOR_CON
 MAX_WINDOW = 16        # mfcf.hip MF_MAX_WINDOW
 STEP_DRIFT, STEP_ORIENT, STEP_HEADING, STEP_ALL_ROWS = 1, 2, 4, 8
 BIT_DRIFT_X, BIT_DRIFT_Y, BIT_ORIENT_X, BIT_ORIENT_MAX, BIT_TURNED, BIT_FLIPPED = 1, 2, 4, 8, 16, 32
-
-
-def _gpu_modules():
-    import torch
-    from . import _lib
-    return torch, _lib
 
 
 def _check_points(points):
@@ -93,7 +88,7 @@ class MFCFGPU:
     # -- stages (device tensors in, device tensors out) --
     def upload(self, points, scores=None):
         """A sweep's x y z rows in their dtype (and its float16 PP scores) on the device."""
-        torch, _ = _gpu_modules()
+        torch, _ = gpu_modules()
         points = _check_points(points)
         pts = torch.from_numpy(np.ascontiguousarray(points[:, 0:3])).to(self.device)
         if scores is None:
@@ -104,7 +99,7 @@ class MFCFGPU:
     def gather(self, sweeps, poses, windows, current, thresh):
         """sweeps: list of (pts, h) device pairs; poses: their 4x4 matrices; windows[f]: indices into sweeps in loop order;
         current[f]: the frame's own sweep. Returns (rows [n, 3] float32, off [F + 1] device, count [F] device, off host)."""
-        torch, _lib = _gpu_modules()
+        torch, _lib = gpu_modules()
         lib, F, S = _lib.lib(), len(windows), len(sweeps)
         rows = np.array([int(p.shape[0]) for p, _ in sweeps], np.int32)
         if any(len(w) > MAX_WINDOW for w in windows):
@@ -137,7 +132,7 @@ class MFCFGPU:
 
     def voxel_sample(self, rows, off, count, n_frames, res=0.1):
         """Returns (out [n, 3], out_src [n], out_off [F + 2], err [1])."""
-        torch, _lib = _gpu_modules()
+        torch, _lib = gpu_modules()
         lib, n = _lib.lib(), int(rows.shape[0])
         out = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)
         src = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
@@ -152,7 +147,7 @@ class MFCFGPU:
 
     def fit_dgd(self, xyz, off, cnt, labels, boxes, n_frames, cap, steps=STEP_DRIFT | STEP_ORIENT | STEP_HEADING):
         """boxes: cpd_outline_boxes' output for the same frames and cap. Returns (out [cap, 7], bits [cap], n_out [1])."""
-        torch, _lib = _gpu_modules()
+        torch, _lib = gpu_modules()
         out = torch.empty((max(cap, 1), 7), dtype=torch.float64, device=self.device)
         bits = torch.zeros(max(cap, 1), dtype=torch.int32, device=self.device)
         n_out = torch.empty(1, dtype=torch.int32, device=self.device)
@@ -165,7 +160,7 @@ class MFCFGPU:
     def sampled_boxes(self, rows, off, count, n_frames, stages=False):
         """rows / off / count: gather's output (or any float32 slices). Per frame the box_fit_DGD boxes ([K, 7] float64, or []
         as the reference returns it); with stages also the branch bits per frame and the voxel-sampled rows per frame."""
-        torch, _lib = _gpu_modules()
+        torch, _lib = gpu_modules()
         from .cproto import _copy_back
         vox, _, vox_off, verr = self.voxel_sample(rows, off, count, n_frames)
         F1 = n_frames + 1                                    # the zeroed tail is one more frame without non-ground rows
@@ -208,7 +203,7 @@ _GPU = {}
 
 
 def _gpu(device=None, cfg=None):
-    torch, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     dev = torch.device(device if device is not None else "cuda")
     key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     g = _GPU.get(key)
@@ -222,7 +217,7 @@ def _gpu(device=None, cfg=None):
 def voxel_sampling(point2, res_x=0.1, res_y=0.1, res_z=0.1, device=None):
     """outline_utils.py:368-389 for float32 rows [N, >=3]: one row per 0.1 m cell, cells in the order of their first row, each
     with its last row (all columns). float32 only: the cell arithmetic runs in the rows' dtype."""
-    torch, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     point2 = np.asarray(point2)
     if point2.dtype != np.float32:
         raise TypeError("cpd_amd.mfcf: voxel_sampling takes float32 rows (got %s): the cell quotient is computed in the "
@@ -237,7 +232,7 @@ def voxel_sampling(point2, res_x=0.1, res_y=0.1, res_z=0.1, device=None):
     i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=g.device)
     _, src, out_off, err = g.voxel_sample(rows, i32([0, n]), i32([n]), 1, res_x)
     if int(err.item()):
-        _, _lib = _gpu_modules()
+        _, _lib = gpu_modules()
         raise _lib.CpdHipError("cpd_mfcf_voxel_sample failed: CPD_ERR_UNSUPPORTED (a NaN coordinate, or a cloud wider than "
                                "2^21 cells)")
     m = int(out_off[1].item())
@@ -246,7 +241,7 @@ def voxel_sampling(point2, res_x=0.1, res_y=0.1, res_z=0.1, device=None):
 
 def _dgd_one(g, points_list, boxes, steps):
     """The corrections on given boxes [K, 7], box k with the rows of points_list[k]."""
-    torch, _ = _gpu_modules()
+    torch, _ = gpu_modules()
     xyz = np.concatenate([outline._exact_f32(np.asarray(p)[:, 0:3]) for p in points_list], 0)
     lab = np.concatenate([np.full(len(p), i, np.int32) for i, p in enumerate(points_list)])
     n, k = len(xyz), len(points_list)
@@ -285,7 +280,7 @@ class OutlineFitter(outline.OutlineFitter):
     def box_fit_DGD(self, points_list, offset=0.2, return_bits=False):
         if offset != 0.2:
             raise NotImplementedError("cpd_amd.mfcf: box_fit_DGD's offset is fixed at 0.2 in the kernel")
-        torch, _ = _gpu_modules()
+        torch, _ = gpu_modules()
         points_list = [p for p in points_list if len(p)]     # an empty cluster raises in the reference: skipped
         if not points_list:
             return ([], np.zeros(0, np.int32)) if return_bits else []
@@ -305,11 +300,11 @@ class OutlineFitter(outline.OutlineFitter):
 # ---- the generator ---------------------------------------------------------------------------------------------------------------
 
 def _load_pair(seq_dir, j):
-    path = os.path.join(seq_dir, str(j).zfill(4) + '.npy')
+    path = frame_path(seq_dir, j)
     if not os.path.exists(path):
         return None
     pts = np.load(path)[:, 0:3]
-    h_path = os.path.join(seq_dir, 'ppscore', str(j).zfill(4) + '.npy')
+    h_path = frame_path(os.path.join(seq_dir, 'ppscore'), j)
     if not os.path.exists(h_path):
         raise FileNotFoundError("cpd_amd.mfcf: %s is missing (run cpd_amd.ppscore.create_ppscore first)" % h_path)
     return pts, np.load(h_path)
@@ -344,22 +339,12 @@ class MFCF:
         window(frame_num, frame_num, inte, lambda j: j < n)
         own_pool = pool is None
         pool = ThreadPoolExecutor(4) if own_pool else pool
-        reads, dev = {}, {}
 
-        def want(j):
-            if 0 <= j < n and j not in reads and j not in dev:
-                reads[j] = pool.submit(_load_pair, seq_dir, j)
+        def upload(j, pair):
+            _check_scores(pair[1], len(pair[0]), " (%s frame %d)" % (self.seq_name, j))
+            return self.gpu.upload(*pair)
 
-        def sweep(j):
-            if j not in dev:
-                want(j)
-                pair = reads.pop(j).result()
-                if pair is None:
-                    dev[j] = None
-                else:
-                    _check_scores(pair[1], len(pair[0]), " (%s frame %d)" % (self.seq_name, j))
-                    dev[j] = self.gpu.upload(*pair)
-            return dev[j]
+        cache = SweepCache(pool, n, lambda j: _load_pair(seq_dir, j), upload)
 
         def span(c0):      # the frames the chunk that starts at c0 touches
             return range(max(0, c0 - frame_num), min(n, min(n, c0 + self.chunk) - 1 + frame_num))
@@ -367,22 +352,21 @@ class MFCF:
         all_labels, all_bits, all_vox = [], [], []
         try:
             for j in span(0):
-                want(j)
+                cache.want(j)
             for c0 in range(0, n, self.chunk):
                 c1 = min(n, c0 + self.chunk)
-                for j in [j for j in dev if j < c0 - frame_num]:
-                    del dev[j]
+                cache.drop_before(c0 - frame_num)
                 # negative j never exists as a file; j >= len(infos) would fail on infos[j] in the reference, here it is skipped
-                wins = [window(i, frame_num, inte, lambda j: j < n and sweep(j) is not None) for i in range(c0, c1)]
+                wins = [window(i, frame_num, inte, lambda j: j < n and cache.get(j) is not None) for i in range(c0, c1)]
                 for i, w in zip(range(c0, c1), wins):
                     if i not in w:
                         raise FileNotFoundError("cpd_amd.mfcf: %s is missing: frame %d is not in its own window"
-                                                % (os.path.join(seq_dir, str(i).zfill(4) + '.npy'), i))
+                                                % (frame_path(seq_dir, i), i))
                 for j in span(c1):                           # the next chunk's reads overlap this chunk's kernels
-                    want(j)
+                    cache.want(j)
                 used = sorted(set(j for w in wins for j in w))
                 index = {j: k for k, j in enumerate(used)}
-                res = self.gpu.frames_boxes([dev[j] for j in used], [infos[j]['pose'] for j in used],
+                res = self.gpu.frames_boxes([cache.get(j) for j in used], [infos[j]['pose'] for j in used],
                                             [[index[j] for j in w] for w in wins], [index[i] for i in range(c0, c1)], thresh,
                                             stages)
                 if stages:
@@ -423,32 +407,13 @@ class MFCF:
 def create_mfcf(seq_names, root_path, dataset_cfg, device=None, chunk=16):
     """Single-process sequence driver in place of the dataset's multiprocessing.Pool(16) (forked workers must not each open the
     GPU): every sequence through one GPU context, the .npy and ppscore reads on a small thread pool while the GPU works."""
-    out, gpu = [], None
     with ThreadPoolExecutor(4) as pool:
-        for s in seq_names:
-            m = MFCF(s, root_path, dataset_cfg, device, chunk)
-            m._gpu = gpu
-            out.append(m.generate_outline_box(pool))
-            gpu = m._gpu
-    return out
+        return run_sequences(lambda s: MFCF(s, root_path, dataset_cfg, device, chunk), seq_names,
+                             lambda m: m.generate_outline_box(pool))
 
 
 def compute_outline_box(seq_name, root_path, dataset_cfg):
     """cpd/unsupervised_core/__init__.py compute_outline_box for what has a GPU drop-in: InitLabelGenerator 'DBSCAN'
     (outline.DBSCAN) and 'MFCF', LabelRefiner 'C_PROTO' (cproto_refine.C_PROTO). outline.compute_outline_box keeps its own,
     narrower contract."""
-    suc = None
-    if _has(dataset_cfg, 'InitLabelGenerator'):
-        method = _get(dataset_cfg, 'InitLabelGenerator')
-        all_init = {'DBSCAN': outline.DBSCAN, 'MFCF': MFCF}
-        if method not in all_init:
-            raise NotImplementedError("cpd_amd.mfcf: InitLabelGenerator %r has no GPU drop-in (only 'DBSCAN' and 'MFCF')"
-                                      % (method,))
-        suc = all_init[method](seq_name, root_path, dataset_cfg)()
-    if _has(dataset_cfg, 'LabelRefiner'):
-        refiner = _get(dataset_cfg, 'LabelRefiner')
-        if refiner != 'C_PROTO':
-            raise NotImplementedError("cpd_amd.mfcf: LabelRefiner %r has no GPU drop-in (only 'C_PROTO')" % (refiner,))
-        from .cproto_refine import C_PROTO
-        suc = C_PROTO(seq_name, root_path, dataset_cfg)()
-    return suc
+    return dispatch_outline_box(seq_name, root_path, dataset_cfg, {'DBSCAN': outline.DBSCAN, 'MFCF': MFCF}, ('C_PROTO',), "mfcf")

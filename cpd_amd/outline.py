@@ -9,12 +9,12 @@ rectangle -- here every hull edge is a candidate.
 import ctypes
 import os
 import pickle as pkl
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import _lib
+from .seq_io import _get, _has, dispatch_outline_box, dtype_runs, frame_path, prefetched_chunks
 
 # GeneratorConfig of tools/cfgs/dataset_configs/waymo_unsupervised/waymo_unsupervised_dbscan.yaml
 DBSCAN_GENERATOR_CONFIG = dict(
@@ -29,12 +29,6 @@ DBSCAN_GENERATOR_CONFIG = dict(
 
 MAX_BANDS = 6          # len(ground_min_threshold) the kernels take (outline.hip OL_MAX_BANDS)
 BOX_CAP_PER_FRAME = 256
-
-
-def _get(cfg, name, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(name, default)
-    return getattr(cfg, name, default)
 
 
 _CLASS_CHAIN = ['Dis_Small', 'Pedestrian', 'Cyclist', 'Vehicle', 'Dis_Large']   # the range tests, in the reference's order
@@ -329,14 +323,8 @@ def outline_frames(frames, generator_cfg, device=None, chunk=16, gpu=None):
     """Per frame (outline_box, outline_cls, outline_dif) as DBSCAN.generate_outline_box stores them: one set of launches and
     one read-back per chunk of frames."""
     gpu = gpu or OutlineGPU(_params(generator_cfg), device)
-    res, runs, c0 = [], [], 0
-    while c0 < len(frames):    # chunks of at most `chunk` frames of one dtype (the projection arithmetic is per dtype)
-        c1 = c0 + 1
-        while c1 < len(frames) and c1 - c0 < chunk and np.asarray(frames[c1]).dtype == np.asarray(frames[c0]).dtype:
-            c1 += 1
-        runs.append((c0, c1))
-        c0 = c1
-    for c0, c1 in runs:
+    res = []
+    for c0, c1 in dtype_runs(frames, chunk):
         for boxes in gpu.frames_boxes(frames[c0:c1]):
             b, cls, dif = get_box_cls(boxes, generator_cfg)
             b, cls, _, dif, _, _ = drop_cls(b, cls, dif=dif)
@@ -366,18 +354,10 @@ class DBSCAN:
         with open(in_pkl, 'rb') as f:
             infos = pkl.load(f)
         gcfg = _get(self.dataset_cfg, "GeneratorConfig")
-        paths = [os.path.join(self.root_path, self.seq_name, str(i).zfill(4) + '.npy') for i in range(len(infos))]
-        with ThreadPoolExecutor(4) as pool:
-            chunks = [paths[c:c + self.chunk] for c in range(0, len(paths), self.chunk)]
-            fut = pool.submit(lambda c: [np.load(p)[:, 0:3] for p in c], chunks[0]) if chunks else None
-            i = 0
-            for k in range(len(chunks)):
-                frames = fut.result()
-                if k + 1 < len(chunks):   # next chunk's reads overlap this chunk's kernels
-                    fut = pool.submit(lambda c: [np.load(p)[:, 0:3] for p in c], chunks[k + 1])
-                for b, cls, dif in outline_frames(frames, gcfg, chunk=self.chunk, gpu=self.gpu):
-                    infos[i]['outline_box'], infos[i]['outline_cls'], infos[i]['outline_dif'] = b, cls, dif
-                    i += 1
+        paths = [frame_path(os.path.join(self.root_path, self.seq_name), i) for i in range(len(infos))]
+        for idx, frames in prefetched_chunks(paths, self.chunk):   # the next chunk's reads overlap this chunk's kernels
+            for i, (b, cls, dif) in zip(idx, outline_frames(frames, gcfg, chunk=self.chunk, gpu=self.gpu)):
+                infos[i]['outline_box'], infos[i]['outline_cls'], infos[i]['outline_dif'] = b, cls, dif
         with open(out_pkl, 'wb') as f:
             pkl.dump(infos, f)
         return infos
@@ -390,20 +370,8 @@ all_init = {'DBSCAN': DBSCAN}
 
 
 def compute_outline_box(seq_name, root_path, dataset_cfg):
-    """cpd/unsupervised_core/__init__.py compute_outline_box for InitLabelGenerator 'DBSCAN'."""
-    suc = None
-    if _has(dataset_cfg, 'InitLabelGenerator'):
-        method = _get(dataset_cfg, 'InitLabelGenerator')
-        if method not in all_init:
-            raise NotImplementedError("cpd_amd.outline: InitLabelGenerator %r has no GPU drop-in (only 'DBSCAN')" % method)
-        suc = all_init[method](seq_name, root_path, dataset_cfg)()
-    if _has(dataset_cfg, 'LabelRefiner'):
-        raise NotImplementedError("cpd_amd.outline: LabelRefiner %r has no GPU drop-in" % _get(dataset_cfg, 'LabelRefiner'))
-    return suc
-
-
-def _has(cfg, name):
-    return name in cfg if isinstance(cfg, dict) else hasattr(cfg, name)
+    """cpd/unsupervised_core/__init__.py compute_outline_box for InitLabelGenerator 'DBSCAN'; every LabelRefiner is refused."""
+    return dispatch_outline_box(seq_name, root_path, dataset_cfg, all_init, (), "outline")
 
 
 def create_outline_boxes(seq_names, root_path, dataset_cfg, device=None, chunk=16):

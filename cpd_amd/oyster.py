@@ -15,7 +15,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import outline
-from .outline import DBSCAN_GENERATOR_CONFIG, _get, _has, _paths, drop_cls
+from .outline import DBSCAN_GENERATOR_CONFIG, _get, _paths, drop_cls
+from .seq_io import dispatch_outline_box, dtype_runs, frame_path, gpu_modules, prefetched_chunks, run_sequences
 from .tracker import TrackSmooth
 
 # GeneratorConfig of tools/cfgs/dataset_configs/waymo_unsupervised/waymo_unsupervised_oyster.yaml: the OutlineFitter arguments and
@@ -31,12 +32,6 @@ MIN_TRACK_LEN = 6      # oyster.py:93, 123: shorter tracks are neither aligned n
 TOP_FRACTION = 0.95    # oyster.py:106
 
 
-def _gpu_modules():
-    import torch
-    from . import _lib
-    return torch, _lib
-
-
 def track_top(n):
     """oyster.py:106-108: the number of nearest boxes whose size is averaged, as Python evaluates it (1 - 0.95 is
     0.050000000000000044: 3 up to n = 79, 4 from n = 80, 5 from n = 100)."""
@@ -46,7 +41,7 @@ def track_top(n):
 def launch_align(d_boxes, d_off, d_top, d_out):
     """cpd_oyster_align_tracks on device tensors, on the current stream: d_boxes / d_out [N, 7] float64, d_off [T + 1] and d_top
     [T] int32. Nothing is checked or read back here."""
-    _, _lib = _gpu_modules()
+    _, _lib = gpu_modules()
     _lib.check(_lib.lib().cpd_oyster_align_tracks(_lib.ptr(d_boxes), _lib.ptr(d_off), _lib.ptr(d_top), int(d_top.shape[0]),
                                                   int(d_boxes.shape[0]), _lib.ptr(d_out), _lib.stream()),
                "cpd_oyster_align_tracks")
@@ -57,7 +52,7 @@ def align_tracks(boxes, track_off, device=None):
     """oyster.py:89-115 with corner_align for every track in one launch. boxes [N, 7] float64 in track-major order (each
     track's rows in frame order), track_off [T + 1] their offsets; returns the aligned boxes [N, 7] float64. The offsets are
     checked here, on the host, before they travel."""
-    torch, _lib = _gpu_modules()
+    torch, _lib = gpu_modules()
     boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1, 7)
     off = np.asarray(track_off)
     if off.ndim != 1 or len(off) < 1 or not np.issubdtype(off.dtype, np.integer):
@@ -107,10 +102,6 @@ def write_frames(infos, tracks):
     return infos
 
 
-def _load_xyz(path):
-    return np.load(path)[:, 0:3]
-
-
 class OYSTER:
     """oyster.py OYSTER: the same file contract. Behaviours of the reference kept on purpose:
       * the input is <seq>_outline_MFCF.pkl where it exists, else <seq>.pkl; a frame whose info carries 'outline_box' brings
@@ -146,31 +137,11 @@ class OYSTER:
         """oyster.py:48-64: every frame's detections (and the poses)."""
         seq_dir = os.path.join(self.root_path, self.seq_name)
         all_labels = [info['outline_box'] if 'outline_box' in info else None for info in infos]
-        need = [i for i, b in enumerate(all_labels) if b is None]
-        chunks = [need[c:c + self.chunk] for c in range(0, len(need), self.chunk)]
-        if chunks:
-            own_pool = pool is None
-            pool = ThreadPoolExecutor(4) if own_pool else pool
-
-            def read(c):
-                return [pool.submit(_load_xyz, os.path.join(seq_dir, str(i).zfill(4) + '.npy')) for i in c]
-            try:
-                futs = read(chunks[0])
-                for k, c in enumerate(chunks):
-                    frames = [f.result() for f in futs]
-                    if k + 1 < len(chunks):                   # the next chunk's reads overlap this chunk's kernels
-                        futs = read(chunks[k + 1])
-                    r0 = 0
-                    while r0 < len(c):                        # one dtype per launch sequence (the projection arithmetic is per dtype)
-                        r1 = r0 + 1
-                        while r1 < len(c) and frames[r1].dtype == frames[r0].dtype:
-                            r1 += 1
-                        for i, boxes in zip(c[r0:r1], self.gpu.frames_boxes(frames[r0:r1])):
-                            all_labels[i] = boxes
-                        r0 = r1
-            finally:
-                if own_pool:
-                    pool.shutdown()
+        need = [(i, frame_path(seq_dir, i)) for i, b in enumerate(all_labels) if b is None]
+        for idx, frames in prefetched_chunks(need, self.chunk, pool=pool):   # the next chunk's reads overlap this chunk's kernels
+            for r0, r1 in dtype_runs(frames, self.chunk):                    # one dtype per launch sequence
+                for i, boxes in zip(idx[r0:r1], self.gpu.frames_boxes(frames[r0:r1])):
+                    all_labels[i] = boxes
         return all_labels, [info['pose'] for info in infos]
 
     def generate_outline_box(self, pool=None):
@@ -203,32 +174,15 @@ class OYSTER:
 def create_oyster(seq_names, root_path, dataset_cfg, device=None, chunk=16):
     """Single-process sequence driver in place of the dataset's multiprocessing.Pool(16) (forked workers must not each open the
     GPU): every sequence through one GPU context, the .npy reads on a small thread pool while the GPU works."""
-    out, gpu = [], None
     with ThreadPoolExecutor(4) as pool:
-        for s in seq_names:
-            o = OYSTER(s, root_path, dataset_cfg, device, chunk)
-            o._gpu = gpu
-            out.append(o.generate_outline_box(pool))
-            gpu = o._gpu
-    return out
+        return run_sequences(lambda s: OYSTER(s, root_path, dataset_cfg, device, chunk), seq_names,
+                             lambda o: o.generate_outline_box(pool))
 
 
 def compute_outline_box(seq_name, root_path, dataset_cfg):
     """cpd/unsupervised_core/__init__.py compute_outline_box: InitLabelGenerator 'DBSCAN' (outline.DBSCAN), 'OYSTER' and 'MFCF'
     (mfcf.MFCF), then LabelRefiner 'C_PROTO' (cproto_refine.C_PROTO). mfcf's and outline's own dispatchers keep their narrower
     contracts."""
-    suc = None
-    if _has(dataset_cfg, 'InitLabelGenerator'):
-        from .mfcf import MFCF
-        method = _get(dataset_cfg, 'InitLabelGenerator')
-        all_init = {'DBSCAN': outline.DBSCAN, 'OYSTER': OYSTER, 'MFCF': MFCF}
-        if method not in all_init:
-            raise NotImplementedError("cpd_amd.oyster: InitLabelGenerator %r is none of 'DBSCAN', 'OYSTER', 'MFCF'" % (method,))
-        suc = all_init[method](seq_name, root_path, dataset_cfg)()
-    if _has(dataset_cfg, 'LabelRefiner'):
-        refiner = _get(dataset_cfg, 'LabelRefiner')
-        if refiner != 'C_PROTO':
-            raise NotImplementedError("cpd_amd.oyster: LabelRefiner %r has no GPU drop-in (only 'C_PROTO')" % (refiner,))
-        from .cproto_refine import C_PROTO
-        suc = C_PROTO(seq_name, root_path, dataset_cfg)()
-    return suc
+    from .mfcf import MFCF
+    return dispatch_outline_box(seq_name, root_path, dataset_cfg, {'DBSCAN': outline.DBSCAN, 'OYSTER': OYSTER, 'MFCF': MFCF},
+                                ('C_PROTO',), "oyster")

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .seq_io import SweepCache, frame_path
 
 MAX_TRAVERSALS = 16    # ppscore.hip PP_MAX_TRAV
 
@@ -163,40 +164,25 @@ def _sequence(gpu, pool, seq_name, root_path, max_win, win_inte, max_neighbor_di
     if not os.path.exists(out_dir):
         os.makedirs(out_dir)
     n = len(infos)
-    path = lambda j: os.path.join(seq_dir, str(j).zfill(4) + '.npy')
-    # frame j is read once (on the pool, ahead of its first use), uploaded once and dropped after its last window
-    reads, dev = {}, {}
+    cache = SweepCache(pool, n, lambda j: _load(frame_path(seq_dir, j)), lambda j, host: gpu.upload(host))
     ahead = max_win + 4
-
-    def want(j):
-        if 0 <= j < n and j not in reads and j not in dev:
-            reads[j] = pool.submit(_load, path(j))
-
-    def frame(j):
-        if j not in dev:
-            want(j)
-            host = reads.pop(j).result()
-            dev[j] = None if host is None else gpu.upload(host)
-        return dev[j]
-
     for j in range(min(n, ahead)):
-        want(j)
+        cache.want(j)
     warned = False
     for i in range(n):
-        want(i + ahead - 1)
-        for j in [j for j in dev if j < i - max_win]:
-            del dev[j]
+        cache.want(i + ahead - 1)
+        cache.drop_before(i - max_win)
         # negative j never exists as a file; j >= len(infos) would fail on infos[j] in the reference, here it is skipped
-        js = [j for j in range(i - max_win, i + max_win, win_inte) if 0 <= j < n and frame(j) is not None]
+        js = [j for j in range(i - max_win, i + max_win, win_inte) if 0 <= j < n and cache.get(j) is not None]
         if i not in js:
             raise FileNotFoundError("cpd_amd.ppscore: frame %s is not in its own window (max_win %d, win_inte %d) or its "
-                                    "file is missing" % (path(i), max_win, win_inte))
+                                    "file is missing" % (frame_path(seq_dir, i), max_win, win_inte))
         if len(js) < 2 and not warned:
             warnings.warn("cpd_amd.ppscore: %s has frames with fewer than two traversals; their PP score is NaN" % seq_name)
             warned = True
-        _, h = gpu.run(dev[i], [dev[j] for j in js], [infos[j]['pose'] for j in js], np.linalg.inv(infos[i]['pose']),
-                       max_neighbor_dist, want_counts=False)
-        np.save(os.path.join(out_dir, str(i).zfill(4) + '.npy'), h.cpu().numpy())
+        _, h = gpu.run(cache.get(i), [cache.get(j) for j in js], [infos[j]['pose'] for j in js],
+                       np.linalg.inv(infos[i]['pose']), max_neighbor_dist, want_counts=False)
+        np.save(frame_path(out_dir, i), h.cpu().numpy())
     return True
 
 

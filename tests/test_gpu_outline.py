@@ -57,6 +57,9 @@ def _grid(n, step, origin=(10.0, 5.0, 0.5)):
     return np.asarray(origin) + step * np.arange(n)[:, None] * np.array([1.0, 0, 0])
 
 
+BLOB24 = np.array([[0.0625 * i, 0.0625 * j, 0.0625 * k] for i in range(2) for j in range(4) for k in range(3)])   # 2 x 4 x 3
+
+
 def dbscan_cases():
     rng = np.random.default_rng(5)
     cases = {}
@@ -77,6 +80,15 @@ def dbscan_cases():
     cases["duplicates"] = np.repeat(np.array([[50.0, 1.0, 0.5], [50.3, 1.0, 0.5]]), 6, 0).astype(np.float64)
     cases["all_noise"] = np.float32(rng.uniform(-40, 40, (300, 3)) * [1, 1, 0.01]).astype(np.float64)
     cases["empty"] = np.zeros((0, 3))
+    # the shared grid (csrc/hash_grid.h): cells 2 and 2 + 2^18 of side 0.5 share a slot; every candidate is still decided by
+    # its distance, so two clumps 2^17 apart are two clusters, and twelve rows in one slot, six in each place, are not core
+    blob24 = BLOB24 + [1.0, 1.0, 0.5]
+    far = [2.0 ** 17, 0.0, 0.0]
+    cases["alias_two_clusters"] = np.concatenate([blob24, blob24 + far])
+    cases["alias_not_core"] = np.concatenate([blob24[:6], blob24[:6] + far])
+    # cells -1 and 0 on all three axes: floor, not truncation
+    cases["negative_cells"] = np.array([[0.0625 * i, 0.0625 * j, 0.0625 * k] for i in range(-2, 2) for j in range(-2, 2)
+                                        for k in range(-1, 1)])
     return {k: v.astype(np.float32).astype(np.float64) for k, v in cases.items()}   # float32 values, as remove_ground gives
 
 
@@ -92,8 +104,28 @@ def test_dbscan_hand_built(fitter, name):
         assert (want >= 0).any()
     if name == "exact_eps":
         assert want.max() == 0 and (want == 0).all()
-    if name in ("nine_neighbours", "all_noise", "empty"):
+    if name in ("nine_neighbours", "all_noise", "empty", "alias_not_core"):
         assert (want == -1).all() and ncl == 0
+    if name == "alias_two_clusters":
+        assert (want[:24] == 0).all() and (want[24:] == 1).all() and ncl == 2
+    if name == "negative_cells":
+        assert len(want) == 32 and (want == 0).all() and ncl == 1
+
+
+def test_dbscan_frames_do_not_mix(fitter):
+    """Two frames in one launch share the grid and differ only in the tag of their keys: the same cell of two frames must not
+    pool its rows."""
+    import torch
+    g = fitter.gpu
+    blob = (BLOB24 + [1.0, 1.0, 0.5]).astype(np.float32)
+    for rows, want_label, want_ncl in ((blob, 0, [1, 1]), (blob[:6], -1, [0, 0])):
+        n = len(rows)
+        xyz = torch.from_numpy(np.concatenate([rows, rows])).to(g.device)
+        off = torch.tensor([0, n, 2 * n], dtype=torch.int32, device=g.device)
+        cnt = torch.tensor([n, n], dtype=torch.int32, device=g.device)
+        labels, ncl = g.dbscan(xyz, off, cnt, 2)
+        assert (labels[:2 * n].cpu().numpy() == want_label).all()
+        assert ncl.cpu().numpy().tolist() == want_ncl
 
 
 def test_dbscan_dense_blob(fitter):
