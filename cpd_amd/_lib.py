@@ -178,6 +178,11 @@ SIGNATURES = {
     "cpd_mfcf_voxel_sample": (_I, [_VP, _VP, _VP, _I, _I, _F, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_mfcf_fit_dgd": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP]),
     "cpd_oyster_align_tracks": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP]),
+    "cpd_augment_scene_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cpd_augment_scene": (_I, [_VP, _I, _I, _VP, ctypes.c_longlong, _I, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _I, _FP, _VP, _VP,
+                               _VP, _SZ, _VP]),
+    "cpd_group_points_by_box_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_group_points_by_box": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 

@@ -11,6 +11,7 @@
 // reference's dz, dy, dx order ("first nsample hits"), and the group stops as soon as nsample
 // neighbours are found. With the bitmap index a cell test is one bit of an L2-resident word.
 #include "site_index_layout.h"
+#include "pt_in_box.h"
 
 // Several kernels below must reproduce fp32 torch arithmetic op for op (the anchor assigner compares IoUs
 // for exact equality; points_in_boxes decides on face distances): this file is compiled with
@@ -777,18 +778,7 @@ extern "C" int cpd_merge_sweeps(const float *points, const int32_t *sweep_offset
 }
 
 // ---- prototype box crop (waymo_unsupervised_dataset.py:205-331 sample_prototype_cpu) ------------------------------------
-// check_pt_in_box3d_cpu (roiaware_pool3d.cpp:128-140): |z - cz| > dz / 2.0 rejects; the rectangle test compares
-// fabs(local) with d / 2.0 + MARGIN in DOUBLE (MARGIN = (float)1e-2 promoted), local coordinates from fp32
-// lidar_to_local_coords_cpu (cos / sin of -rz, no contraction).
-__device__ __forceinline__ bool pt_in_box_cpu(float x, float y, float z, const float *q, float ca, float sa) {
-    // q = cx, cy, cz, dx, dy, dz; ca / sa = cos / sin(-rz)
-    if ((double)fabsf(z - q[2]) > (double)q[5] / 2.0) return false;
-    const float sx = x - q[0], sy = y - q[1];
-    const float lx = __fadd_rn(__fmul_rn(sx, ca), __fmul_rn(sy, -sa));
-    const float ly = __fadd_rn(__fmul_rn(sx, sa), __fmul_rn(sy, ca));
-    const double margin = (double)1e-2f;
-    return (double)fabsf(lx) < (double)q[3] / 2.0 + margin && (double)fabsf(ly) < (double)q[4] / 2.0 + margin;
-}
+// (pt_in_box_cpu, check_pt_in_box3d_cpu of roiaware_pool3d.cpp:128-140, and its box staging: pt_in_box.h)
 
 // roiaware_pool3d_utils.points_in_boxes_cpu: out[box][point] = 1 / 0
 __global__ void __launch_bounds__(256) points_in_boxes_mask_kernel(const float *__restrict__ boxes, int k, const float *__restrict__ pts,
@@ -818,9 +808,7 @@ __global__ void __launch_bounds__(256) crop_flags_kernel(const float *__restrict
         __syncthreads();
         for (int j = threadIdx.x; j < nk; j += blockDim.x) {
             const float *bq = boxes + 7 * (size_t)(k0 + j);
-            for (int q = 0; q < 6; ++q) sbox[12 * j + q] = bq[q];
-            sbox[12 * j + 6] = (float)cos((double)(-bq[6]));
-            sbox[12 * j + 7] = (float)sin((double)(-bq[6]));
+            stage_box_cpu(sbox, j, bq);
             sbox[12 * j + 8] = discard[k0 + j] ? 1.f : 0.f;
         }
         __syncthreads();

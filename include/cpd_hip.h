@@ -1024,6 +1024,41 @@ int cpd_mfcf_fit_dgd(const float *xyz, const int32_t *frame_off, const int32_t *
 int cpd_oyster_align_tracks(const double *boxes, const int32_t *track_off, const int32_t *track_top, int n_tracks, int n_rows,
                             double *out, cpd_stream_t stream);
 
+/* ---- training-time augmentor (csrc/augment.hip): the point work of DataAugmentor.forward with gt_sampling
+ * (database_sampler.py:359-416 add_sampled_boxes_to_scene, augmentor_utils.py:8-105, common_utils.py:60-63) in one flag pass
+ * and one scan / emit.
+ *   scene [n][c] f32 (c >= 3); obj_base [obj_rows][c_obj] f32 (c_obj >= c): the database rows; HOST obj_start [k_obj] (first row
+ *   of a pasted object in obj_base), obj_count [k_obj], obj_centre [k_obj][3] float64 -- segments in any order, overlapping or
+ *   not; boxes [k][7] f32 DEVICE: the enlarged sampled boxes (k = 0: nothing is removed); HOST op_kind [n_ops] / op_param
+ *   [n_ops][2], applied in order: CPD_AUG_FLIP_X y = -y; CPD_AUG_FLIP_Y x = -x; CPD_AUG_ROT with param = (cos, sin) as float32
+ *   values: x' = fma(y, -sin, fl(x cos)), y' = fma(y, cos, fl(x sin)); CPD_AUG_SCALE with param[0] = f: v = fl(v * (float)f), a float32 product,
+ *   for x, y, z. range_xyz HOST [6] or NULL: keep a row iff r0 <= x <= r3 && r1 <= y <= r4 after the ops (NaN: dropped).
+ * out [n + m][c], m = sum(obj_count): first the object rows in segment order, columns 0-2 = (float)((double)v + centre),
+ * columns 3..c-1 copied, columns >= c dropped; then the scene rows inside no box (check_pt_in_box3d_cpu, MARGIN 1e-2) in their
+ * order; every row through the ops and the range test; compacted stably; *n_out (device) = rows written.
+ * CPD_ERR_UNSUPPORTED: k > 512, k_obj > 512, n_ops > CPD_AUG_MAX_OPS, n + m >= 2^31. CPD_ERR_ARG: null pointers, negative
+ * sizes, c_obj < c, a segment outside [0, obj_rows), an unknown op. n, m, k, n_ops may each be 0. */
+#define CPD_AUG_FLIP_X 0
+#define CPD_AUG_FLIP_Y 1
+#define CPD_AUG_ROT 2
+#define CPD_AUG_SCALE 3
+#define CPD_AUG_MAX_OPS 8
+size_t cpd_augment_scene_workspace_bytes(int n, int m, int k_obj);
+int cpd_augment_scene(const float *scene, int n, int c, const float *obj_base, long long obj_rows, int c_obj,
+                      const int64_t *obj_start, const int32_t *obj_count, const double *obj_centre, int k_obj,
+                      const float *boxes, int k, const int32_t *op_kind, const double *op_param, int n_ops,
+                      const float *range_xyz, float *out, int32_t *n_out, void *workspace, size_t workspace_bytes,
+                      cpd_stream_t stream);
+
+/* The point work of create_track_groundtruth_database (waymo_unsupervised_dataset.py:711-725). points [n][c] f32, box_idx [n]
+ * int32 (cpd_points_in_boxes: -1 = background; ids >= k are treated as background), HOST centre [k][3] float64. out [n][c]:
+ * the rows with box_idx >= 0 grouped by ascending box, point order kept inside a box, columns 0-2 = (float)((double)v - centre);
+ * offsets [k + 1] device int32: box b is rows offsets[b] .. offsets[b + 1]. CPD_ERR_UNSUPPORTED: k > 1024. Any n an int holds;
+ * the workspace holds two (box, block) tables of ceil(n / 2048) * k words each (8 MB at n = 2^21, k = 1024): ask the query. */
+size_t cpd_group_points_by_box_workspace_bytes(int n, int k);
+int cpd_group_points_by_box(const float *points, int n, int c, const int32_t *box_idx, int k, const double *centre, float *out,
+                            int32_t *offsets, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
