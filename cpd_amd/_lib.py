@@ -149,6 +149,10 @@ SIGNATURES = {
     "cpd_kitti_match_scores": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_kitti_match_pr": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _I,
                                 _I, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_waymo_iou": (_I, [_VP, _VP, _VP, _VP, _VP, _I, ctypes.c_int64, _VP, _VP]),
+    "cpd_waymo_match_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_waymo_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.POINTER(_D), _I, _I, _I, _VP, _VP, _VP,
+                             _SZ, _VP]),
     "cpd_adam_step": (_I, [_VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _F, _F, _I, _F, _VP, _VP]),
     "cpd_outline_ground_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_outline_ground": (_I, [_VP, _I, _I, _VP, _I, _I, _FP, _D, ctypes.POINTER(_D), ctypes.POINTER(_D), _I, _VP, _VP, _VP,

@@ -238,6 +238,44 @@ def _kitti_dict(a):
     return out
 
 
+_WAYMO_SIZES = {"Vehicle": (4.6, 2.0, 1.6), "Pedestrian": (0.8, 0.7, 1.7), "Cyclist": (1.8, 0.7, 1.7)}
+
+
+def waymo_infos(n_frames, seed=0, n_gt=60, n_pd=150):
+    """Seeded (prediction_infos, gt_infos) in the format Dataset.evaluation hands cpd_amd.waymo_eval (lidar-frame centre
+    boxes: call waymo_evaluation with fake_gt_infos=False): about n_gt ground truths per frame (Vehicle / Pedestrian /
+    Cyclist, point counts spanning both levels and zero) and about n_pd predictions: jittered copies of four fifths of
+    the ground truths, a second lower-scored copy of a third of them, and unrelated boxes for the rest."""
+    rng = np.random.default_rng(seed)
+    names = np.array(list(_WAYMO_SIZES))
+    sizes = np.array([_WAYMO_SIZES[n] for n in names])
+    pds, gts = [], []
+
+    def boxes(kind, n):
+        r, phi = rng.uniform(3, 75, n), rng.uniform(-np.pi, np.pi, n)
+        dims = sizes[kind] * rng.uniform(0.85, 1.15, (n, 3))
+        return np.column_stack([r * np.cos(phi), r * np.sin(phi), rng.uniform(-0.5, 1.5, n), dims, rng.uniform(-np.pi, np.pi, n)])
+
+    for _ in range(n_frames):
+        ng = int(rng.integers(max(1, n_gt - n_gt // 4), n_gt + n_gt // 4 + 1))
+        kind = rng.choice(3, ng, p=[0.55, 0.35, 0.1])
+        g = boxes(kind, ng)
+        gts.append({"name": names[kind], "difficulty": np.zeros(ng, np.int32),
+                    "num_points_in_gt": rng.choice([0, 3, 5, 12, 80, 400], ng, p=[0.03, 0.1, 0.07, 0.2, 0.3, 0.3]).astype(np.int64),
+                    "gt_boxes_lidar": g.astype(np.float32)})
+        hit = np.nonzero(rng.random(ng) < 0.8)[0]
+        twice = hit[rng.random(len(hit)) < 0.33]
+        src = np.concatenate([hit, twice])
+        jit = g[src] + rng.normal(0, 1.0, (len(src), 7)) * np.array([0.12, 0.12, 0.05, 0.1, 0.05, 0.05, 0.06])
+        score = np.concatenate([rng.uniform(0.3, 1.0, len(hit)), rng.uniform(0.02, 0.5, len(twice))])
+        n_fp = max(0, int(rng.integers(n_pd - n_pd // 5, n_pd + n_pd // 5 + 1)) - len(src))
+        fk = rng.choice(3, n_fp)
+        pds.append({"name": np.concatenate([names[kind[src]], names[fk]]),
+                    "score": np.concatenate([score, rng.uniform(0.01, 0.6, n_fp)]).astype(np.float32),
+                    "boxes_lidar": np.concatenate([jit, boxes(fk, n_fp)]).astype(np.float32)})
+    return pds, gts
+
+
 # ---- pseudo-label scene (cpd_amd.outline) --------------------------------------------------------------------------------
 
 def _ray_obb(d, sensor_z, c, size, yaw):

@@ -817,6 +817,38 @@ int cpd_kitti_match_pr(const double *overlaps, const int64_t *pair_off, const in
                        const int32_t *n_thresholds, int n_sweeps, int total_gt, int total_dt, int64_t *pr_counts,
                        double *pr_sim, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Waymo-protocol detection metrics (csrc/waymo_eval.hip): the per-frame work behind
+ * cpd/datasets/waymo_unsupervised/waymo_eval.py (waymo_evaluation, l.178-216; its metric config, build_config l.86-108:
+ * object types 1..4 with IoU thresholds 0.7 / 0.5 / 0.5 / 0.5, levels 1 and 2, 101 score cut-offs, Hungarian matcher, 3-D boxes).
+ * The metric op itself is outside the reference tree; the protocol computed here is the one cpd_amd/waymo_eval.py states.
+ * A "problem" is one (frame, type): problem q = 4 * frame + (type - 1), n_problems = 4 * n_frames. Problems are CSR segments:
+ * pd_off / gt_off [n_problems + 1] int32 row offsets (device), pair_off [n_problems + 1] int64 offsets of each problem's
+ * prediction x ground-truth block in the packed IoUs (row-major, prediction rows, ground-truth columns). */
+#define CPD_WAYMO_TYPES 4
+#define CPD_WAYMO_CUTOFFS 101   /* c_k = (float)(k * 0.01) for k < 100, c_100 = 1 */
+#define CPD_WAYMO_MAX_PD 4096   /* predictions per problem  */
+#define CPD_WAYMO_MAX_GT 1024   /* ground truths per problem */
+/* Rotated 3-D IoU of every pair of every problem (the boxes the estimator feeds its op, generate_waymo_type_results l.26-84):
+ * rows (cx, cy, cz, dx, dy, dz, heading) float32, dx along the heading; float64 arithmetic; BEV rectangle intersection times
+ * the z overlap over the union; 0 for an empty intersection, a non-positive union or a non-finite value. out [n_pairs] float64. */
+int cpd_waymo_iou(const float *pd_boxes, const float *gt_boxes, const int32_t *pd_off, const int32_t *gt_off,
+                  const int64_t *pair_off, int n_problems, int64_t n_pairs, double *out, cpd_stream_t stream);
+/* Workspace of cpd_waymo_match (HOST): the score order of total_pd predictions and 101 per-problem results. */
+size_t cpd_waymo_match_workspace_bytes(int n_problems, int total_pd);
+/* The counts the metric op accumulates for waymo_evaluation (l.206-215): per problem and cut-off k the maximum-weight matching
+ * (sum of IoU over pairs with IoU >= iou_thresholds[type - 1], HOST [4]) of the predictions with score >= c_k and all ground
+ * truths; summed over frames in frame order into counts [4][2 levels][101][3] int64 (tp, fp, fn) and ha [4][2][101] float64
+ * (sum over true positives of 1 - |wrap(heading difference)| / pi). A ground truth counts at level 1 when gt_difficulty == 1 and
+ * at level 2 when it is 1 or 2; fp = unmatched predictions. pd_score / pd_heading [total_pd] float32, gt_difficulty [total_gt]
+ * uint8, gt_heading [total_gt] float32. max_pd / max_gt: the largest row / column count of a problem (they size the LDS;
+ * beyond CPD_WAYMO_MAX_PD / CPD_WAYMO_MAX_GT: CPD_ERR_UNSUPPORTED; a problem larger than them poisons the result: counts -1,
+ * ha NaN). accumulate != 0 continues from the values in counts / ha (the next chunk of frames of the same set). */
+int cpd_waymo_match(const double *iou, const int64_t *pair_off, const int32_t *pd_off, const int32_t *gt_off, int n_problems,
+                    int total_pd, int total_gt, const float *pd_score, const uint8_t *gt_difficulty, const float *pd_heading,
+                    const float *gt_heading, const double *iou_thresholds, int max_pd, int max_gt, int accumulate,
+                    int64_t *counts, double *ha, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+
 /* Diagnostic (csrc/diag.hip; replaces nothing in the reference): the matrix pipe's sustained rate on THIS part under its socket power
  * cap -- `blocks` workgroups of four waves, each wave `iters` x 16 v_mfma_f32_16x16x32_f16 on register operands (a 64 x 64 x 32 tile
  * step), nothing else in the loop. a_operands / b_operands: 512 x 16 bytes of fp16 values each (what the operand DATA is matters: the
