@@ -120,6 +120,11 @@ SIGNATURES = {
     "cpd_voxel_pool_max": (_I, [_I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
     "cpd_voxel_pool_max_mlp": (_I, [_I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _I, _VP]),
     "cpd_voxel_pool_max_mlp_ranged": (_I, [_I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
+    "cpd_voxel_pool_train_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cpd_voxel_pool_moments": (_I, [_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_voxel_pool_max_train": (_I, [_I, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _F, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "cpd_voxel_pool_max_train_grad": (_I, [_I, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP,
+                                           _SZ, _VP]),
     "cpd_bn_stats_finalize": (_I, [_VP, _I, _I, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_bn_finalize": (_I, [_VP, _VP, _I, _I, _F, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cpd_pack_weight_adjoint": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),

@@ -1095,6 +1095,7 @@ extern "C" int cpd_group_points(int b, int m, int c, int nsample, const float *f
         return CPD_ERR_ARG;
     if (m == 0) return CPD_OK;
     const long long total = (long long)m * c * nsample;
+    cpd_launch_log_note("group_points_kernel");
     group_points_kernel<<<cpd_div_up(total, 256), 256, 0, cpd_s(st)>>>(b, m, c, nsample, features, features_batch_cnt, idx,
                                                                         idx_batch_cnt, out);
     return cpd_check_launch();
@@ -1108,6 +1109,7 @@ extern "C" int cpd_group_points_grad(int b, int m, int c, int nsample, int n, co
     if (n > 0) CPD_HIP_TRY(hipMemsetAsync(grad_features, 0, (size_t)n * c * sizeof(float), cpd_s(st)));
     if (m == 0 || n == 0) return CPD_OK;
     const long long total = (long long)m * c * nsample;
+    cpd_launch_log_note("group_points_grad_kernel");
     group_points_grad_kernel<<<cpd_div_up(total, 256), 256, 0, cpd_s(st)>>>(b, m, c, nsample, grad_out, features_batch_cnt, idx,
                                                                              idx_batch_cnt, grad_features);
     return cpd_check_launch();
@@ -1122,5 +1124,295 @@ extern "C" int cpd_voxel_pool_max(int m, int c, int nsample, const float *featur
     if (m == 0) return CPD_OK;
     voxel_pool_max_kernel<<<cpd_div_up((long long)m * c, 256), 256, 0, cpd_s(st)>>>(m, c, nsample, features_in, features_ld, xyz,
                                                                                    new_xyz, idx, w_pos, b_pos, out, out_ld);
+    return cpd_check_launch();
+}
+
+// ---- RoI grid pooling in TRAINING, fused (voxel_pool_modules.py:96-117 with batch-statistics BatchNorm2d) ----------------------------
+// grouping + position encoding (Conv2d 3 -> C, no bias) + BatchNorm2d (batch statistics) + add + ReLU + max over the samples without an
+// (M, C, nsample) tensor. The position branch is linear in p = xyz[idx] - new_xyz (0 for an empty ball), so the batch statistics of
+// channel c follow from the first and second moments of p over all n = M * nsample slots:
+//     mu_c = W_c . S1 / n,   var_c = W_c (S2 / n - S1 S1^T / n^2) W_c^T,        S1 = sum p, S2 = sum p p^T  (float64, fixed tree)
+// and the BatchNorm backward has the closed form written out at pool_train_grad_final_kernel. Three passes:
+//   moments : S1, S2                          (block partials, then one block; bitwise repeatable)
+//   forward : out[m][c] = max_s relu(keep * fin[idx[m][s]][c] + gamma_c zhat + beta_c), arg[m][c] = first s attaining it, 255 when
+//             out == 0 (torch's max-pool / ReLU gradient rules)
+//   backward: dfin by float atomics (as cpd_group_points_grad), dW / dgamma / dbeta from per-block float64 partials in a fixed order.
+// A gather through idx is guarded: a row outside [0, n_rows) counts as an empty slot (p = 0, no feature, no gradient).
+namespace {
+
+constexpr int POOL_MOM_ITEMS = 8;           // (point, sample) slots per thread of the moments pass
+constexpr int POOL_TRAIN_ITERS = 8;         // passes of 256 / C points per block of the forward / backward kernels
+
+__device__ __forceinline__ double wave_sum_f64(double v) {   // butterfly: a fixed tree, every lane ends with the sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// sum of K values per thread over a 256-thread block -> res[k] valid in threads k < K; sm [4][K]
+template <int K>
+__device__ __forceinline__ double block_sum_f64(const double (&a)[K], double (*sm)[K]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double s = wave_sum_f64(a[k]);
+        if (lane == 0) sm[wave][k] = s;
+    }
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x < K) r = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+    return r;
+}
+
+__global__ void __launch_bounds__(256) pool_moments_kernel(long long total, int nsample, int n_rows, const float *__restrict__ xyz,
+                                                           const float *__restrict__ new_xyz, const int32_t *__restrict__ idx,
+                                                           double *__restrict__ part) {
+    __shared__ double sm[4][9];
+    const long long base = (long long)blockIdx.x * (256 * POOL_MOM_ITEMS);
+    double a[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < POOL_MOM_ITEMS; ++k) {
+        const long long i = base + k * 256 + threadIdx.x;
+        if (i >= total) break;
+        const long long pt = i / nsample;
+        const int32_t j = idx[i];
+        if (idx[pt * nsample] < 0 || j < 0 || j >= n_rows) continue;
+        const double x = (double)(xyz[3 * (size_t)j] - new_xyz[3 * pt]), y = (double)(xyz[3 * (size_t)j + 1] - new_xyz[3 * pt + 1]),
+                     z = (double)(xyz[3 * (size_t)j + 2] - new_xyz[3 * pt + 2]);
+        a[0] += x; a[1] += y; a[2] += z;
+        a[3] += x * x; a[4] += x * y; a[5] += x * z; a[6] += y * y; a[7] += y * z; a[8] += z * z;
+    }
+    const double r = block_sum_f64<9>(a, sm);
+    if (threadIdx.x < 9) part[(size_t)blockIdx.x * 9 + threadIdx.x] = r;
+}
+__global__ void __launch_bounds__(256) pool_moments_final_kernel(const double *__restrict__ part, int nb, double *__restrict__ moments) {
+    __shared__ double sm[4][9];
+    double a[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nb; b += 256)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) a[k] += part[(size_t)b * 9 + k];
+    const double r = block_sum_f64<9>(a, sm);
+    if (threadIdx.x < 9) moments[threadIdx.x] = r;
+}
+
+// moments = S1 (x y z), S2 (xx xy xz yy yz zz); w = W_c
+__device__ __forceinline__ void pool_channel_stats(const double *mom, double n, double w0, double w1, double w2, double &mu, double &var) {
+    const double ex = mom[0] / n, ey = mom[1] / n, ez = mom[2] / n;
+    const double cxx = mom[3] / n - ex * ex, cxy = mom[4] / n - ex * ey, cxz = mom[5] / n - ex * ez;
+    const double cyy = mom[6] / n - ey * ey, cyz = mom[7] / n - ey * ez, czz = mom[8] / n - ez * ez;
+    mu = (w0 * ex + w1 * ey) + w2 * ez;
+    var = ((w0 * w0 * cxx + w1 * w1 * cyy) + w2 * w2 * czz) + 2.0 * ((w0 * w1 * cxy + w0 * w2 * cxz) + w1 * w2 * cyz);
+    if (var < 0.0) var = 0.0;
+}
+// mean / invstd of the position branch's BatchNorm and its running statistics (torch's rule: momentum, unbiased variance), as
+// bn_finalize_col of train_ops.hip
+__global__ void __launch_bounds__(64) pool_stats_kernel(int c, double n, const float *__restrict__ wpos, const double *__restrict__ moments,
+                                                        float eps, float momentum, float *__restrict__ running_mean,
+                                                        float *__restrict__ running_var, float *__restrict__ mean, float *__restrict__ invstd) {
+    const int ch = threadIdx.x;
+    if (ch >= c) return;
+    double mu, var;
+    pool_channel_stats(moments, n, (double)wpos[3 * ch], (double)wpos[3 * ch + 1], (double)wpos[3 * ch + 2], mu, var);
+    mean[ch] = (float)mu;
+    invstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) {
+        const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+        running_mean[ch] = (1.f - momentum) * running_mean[ch] + momentum * (float)mu;
+        running_var[ch] = (1.f - momentum) * running_var[ch] + momentum * (float)unbiased;
+    }
+}
+
+// the pre-activation of slot value (dx, dy, dz, f): the one expression forward and backward share
+__device__ __forceinline__ float pool_zhat(float dx, float dy, float dz, float w0, float w1, float w2, float mu, float is) {
+    return (((dx * w0 + dy * w1) + dz * w2) - mu) * is;
+}
+
+// thread = (point slot, channel), channel fastest; a block walks POOL_TRAIN_ITERS x (256 / C) consecutive points
+template <int C>
+__global__ void __launch_bounds__(256) pool_train_fwd_kernel(int m, int nsample, int n_rows, const float *__restrict__ fin, int fin_ld,
+                                                             const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+                                                             const int32_t *__restrict__ idx, const float *__restrict__ wpos,
+                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                             const float *__restrict__ mean, const float *__restrict__ invstd,
+                                                             float *__restrict__ out, int out_ld, uint8_t *__restrict__ arg) {
+    constexpr int PPB = 256 / C;
+    const int slot = threadIdx.x / C, ch = threadIdx.x - slot * C;
+    const float w0 = wpos[3 * ch], w1 = wpos[3 * ch + 1], w2 = wpos[3 * ch + 2];
+    const float g = gamma[ch], b = beta[ch], mu = mean[ch], is = invstd[ch];
+    for (int it = 0; it < POOL_TRAIN_ITERS; ++it) {
+        const long long pt = ((long long)blockIdx.x * POOL_TRAIN_ITERS + it) * PPB + slot;
+        if (pt >= m) break;
+        const int32_t *id = idx + (size_t)pt * nsample;
+        const int32_t j0 = id[0];
+        float best;
+        int bs = 0;
+        if (j0 < 0) {                                               // empty ball: every slot is p = 0 without a feature
+            best = g * pool_zhat(0.f, 0.f, 0.f, w0, w1, w2, mu, is) + b;
+        } else {
+            const float nx = new_xyz[3 * (size_t)pt], ny = new_xyz[3 * (size_t)pt + 1], nz = new_xyz[3 * (size_t)pt + 2];
+            best = -INFINITY;
+#pragma unroll 4
+            for (int s = 0; s < nsample; ++s) {
+                const int32_t j = id[s];
+                if (s > 0 && j == j0) continue;                     // the query's pre-fill (or a repeat of slot 0): its value is slot 0's
+                float dx = 0.f, dy = 0.f, dz = 0.f, f = 0.f;
+                if (j >= 0 && j < n_rows) {
+                    dx = xyz[3 * (size_t)j] - nx; dy = xyz[3 * (size_t)j + 1] - ny; dz = xyz[3 * (size_t)j + 2] - nz;
+                    f = fin[(size_t)j * fin_ld + ch];
+                }
+                const float v = f + (g * pool_zhat(dx, dy, dz, w0, w1, w2, mu, is) + b);
+                if (v > best) { best = v; bs = s; }                 // strict: the first slot attaining the maximum
+            }
+        }
+        const bool pos = best > 0.f;
+        out[(size_t)pt * out_ld + ch] = pos ? best : 0.f;
+        arg[(size_t)pt * C + ch] = pos ? (uint8_t)bs : (uint8_t)255;
+    }
+}
+
+// per block and channel: sum G, sum G zhat*, sum G p* (x y z) over the block's points in float64 -> part[block][5][C]; dfin by atomics
+template <int C>
+__global__ void __launch_bounds__(256) pool_train_grad_kernel(int m, int nsample, int n_rows, const float *__restrict__ gout, int gout_ld,
+                                                              const uint8_t *__restrict__ arg, const int32_t *__restrict__ idx,
+                                                              const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+                                                              const float *__restrict__ wpos, const float *__restrict__ mean,
+                                                              const float *__restrict__ invstd, float *__restrict__ dfin, int dfin_ld,
+                                                              double *__restrict__ part) {
+    constexpr int PPB = 256 / C;
+    __shared__ double sm[PPB][5][C];
+    const int slot = threadIdx.x / C, ch = threadIdx.x - slot * C;
+    const float w0 = wpos[3 * ch], w1 = wpos[3 * ch + 1], w2 = wpos[3 * ch + 2];
+    const float mu = mean[ch], is = invstd[ch];
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int it = 0; it < POOL_TRAIN_ITERS; ++it) {
+        const long long pt = ((long long)blockIdx.x * POOL_TRAIN_ITERS + it) * PPB + slot;
+        if (pt >= m) break;
+        const int s = arg[(size_t)pt * C + ch];
+        if (s == 255 || s >= nsample) continue;                     // ReLU cut the maximum off: no gradient
+        const float gv = gout[(size_t)pt * gout_ld + ch];
+        const int32_t *id = idx + (size_t)pt * nsample;
+        float dx = 0.f, dy = 0.f, dz = 0.f;
+        if (id[0] >= 0) {
+            const int32_t j = id[s];
+            if (j >= 0 && j < n_rows) {
+                dx = xyz[3 * (size_t)j] - new_xyz[3 * (size_t)pt]; dy = xyz[3 * (size_t)j + 1] - new_xyz[3 * (size_t)pt + 1];
+                dz = xyz[3 * (size_t)j + 2] - new_xyz[3 * (size_t)pt + 2];
+                atomicAdd(&dfin[(size_t)j * dfin_ld + ch], gv);
+            }
+        }
+        const double gd = (double)gv;
+        a[0] += gd;
+        a[1] += gd * (double)pool_zhat(dx, dy, dz, w0, w1, w2, mu, is);
+        a[2] += gd * (double)dx; a[3] += gd * (double)dy; a[4] += gd * (double)dz;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) sm[slot][k][ch] = a[k];
+    __syncthreads();
+    if (slot == 0) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            double s = sm[0][k][ch];
+            for (int q = 1; q < PPB; ++q) s += sm[q][k][ch];
+            part[((size_t)blockIdx.x * 5 + k) * C + ch] = s;
+        }
+    }
+}
+// block = channel: the block partials in a fixed order, then
+//   dbeta = A0, dgamma = A1, dW = gamma invstd [ A2..4 - (A0 / n) S1 - (A1 / n) invstd (S2 W - mu S1) ]
+// (BatchNorm's dL/dy_i = gamma invstd [G_i - mean(G) - zhat_i mean(G zhat)] summed against p_i; sum_i zhat_i p_i = invstd (S2 W - mu S1))
+__global__ void __launch_bounds__(256) pool_train_grad_final_kernel(const double *__restrict__ part, int nb, int c, double n,
+                                                                    const float *__restrict__ wpos, const float *__restrict__ gamma,
+                                                                    const double *__restrict__ moments, float eps, float *__restrict__ dw,
+                                                                    float *__restrict__ dgamma, float *__restrict__ dbeta) {
+    __shared__ double sm[4][5];
+    __shared__ double tot[5];
+    const int ch = blockIdx.x;
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = threadIdx.x; b < nb; b += 256)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) a[k] += part[((size_t)b * 5 + k) * c + ch];
+    const double r = block_sum_f64<5>(a, sm);
+    if (threadIdx.x < 5) tot[threadIdx.x] = r;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double w0 = (double)wpos[3 * ch], w1 = (double)wpos[3 * ch + 1], w2 = (double)wpos[3 * ch + 2];
+    double mu, var;
+    pool_channel_stats(moments, n, w0, w1, w2, mu, var);
+    const double is = 1.0 / sqrt(var + (double)eps);
+    const double *S = moments;
+    const double s2w[3] = {(S[3] * w0 + S[4] * w1) + S[5] * w2, (S[4] * w0 + S[6] * w1) + S[7] * w2, (S[5] * w0 + S[7] * w1) + S[8] * w2};
+    dbeta[ch] = (float)tot[0];
+    dgamma[ch] = (float)tot[1];
+    const double gi = (double)gamma[ch] * is;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        dw[3 * ch + k] = (float)(gi * ((tot[2 + k] - tot[0] / n * S[k]) - tot[1] / n * is * (s2w[k] - mu * S[k])));
+}
+
+static inline int pool_moments_blocks(long long total) { return cpd_div_up(total, 256 * POOL_MOM_ITEMS); }
+static inline int pool_train_blocks(int m, int c) { return cpd_div_up(m, POOL_TRAIN_ITERS * (256 / c)); }
+static inline bool pool_train_c_ok(int c) { return c == 16 || c == 32 || c == 64; }
+
+}  // namespace
+
+extern "C" size_t cpd_voxel_pool_train_workspace_bytes(int m, int c, int nsample) {
+    if (m <= 0 || nsample <= 0 || !pool_train_c_ok(c)) return 256;
+    const size_t mom = (size_t)pool_moments_blocks((long long)m * nsample) * 9 * sizeof(double);
+    const size_t grad = (size_t)pool_train_blocks(m, c) * 5 * c * sizeof(double);
+    return cpd_align(mom > grad ? mom : grad);
+}
+
+extern "C" int cpd_voxel_pool_moments(int m, int nsample, int n_rows, const float *xyz, const float *new_xyz, const int32_t *idx,
+                                      double *moments, void *workspace, size_t workspace_bytes, cpd_stream_t st) {
+    if (m < 0 || nsample <= 0 || n_rows < 0 || !moments || !workspace || (m > 0 && (!xyz || !new_xyz || !idx))) return CPD_ERR_ARG;
+    const long long total = (long long)m * nsample;
+    const int nb = pool_moments_blocks(total);
+    if (workspace_bytes < (size_t)nb * 9 * sizeof(double)) return CPD_ERR_WORKSPACE;
+    double *part = static_cast<double *>(workspace);
+    cpd_launch_log_note("voxel_pool_moments_kernel");
+    if (nb > 0) pool_moments_kernel<<<nb, 256, 0, cpd_s(st)>>>(total, nsample, n_rows, xyz, new_xyz, idx, part);
+    pool_moments_final_kernel<<<1, 256, 0, cpd_s(st)>>>(part, nb, moments);
+    return cpd_check_launch();
+}
+
+extern "C" int cpd_voxel_pool_max_train(int m, int c, int nsample, int n_rows, const float *features_in, int features_ld, const float *xyz,
+                                        const float *new_xyz, const int32_t *idx, const float *w_pos, const float *gamma, const float *beta,
+                                        const double *moments, float eps, float momentum, float *running_mean, float *running_var,
+                                        float *out, int out_ld, uint8_t *arg, float *mean, float *invstd, cpd_stream_t st) {
+    if (m <= 0 || c <= 0 || nsample <= 0 || (long long)m * nsample <= 1 || n_rows < 0 || features_ld < c || out_ld < c || !features_in || !xyz ||
+        !new_xyz || !idx || !w_pos || !gamma || !beta || !moments || !out || !arg || !mean || !invstd || (running_mean && !running_var))
+        return CPD_ERR_ARG;
+    if (!pool_train_c_ok(c) || nsample > 255) return CPD_ERR_UNSUPPORTED;     // (arg is a byte; 255 = no gradient)
+    const double n = (double)m * (double)nsample;
+    pool_stats_kernel<<<1, 64, 0, cpd_s(st)>>>(c, n, w_pos, moments, eps, momentum, running_mean, running_var, mean, invstd);
+    const int nb = pool_train_blocks(m, c);
+    cpd_launch_log_note("voxel_pool_max_train_kernel");
+#define CPD_POOL_TRAIN(C) pool_train_fwd_kernel<C><<<nb, 256, 0, cpd_s(st)>>>(m, nsample, n_rows, features_in, features_ld, xyz, new_xyz, idx, w_pos, \
+                                                                             gamma, beta, mean, invstd, out, out_ld, arg)
+    if (c == 16) CPD_POOL_TRAIN(16); else if (c == 32) CPD_POOL_TRAIN(32); else CPD_POOL_TRAIN(64);
+#undef CPD_POOL_TRAIN
+    return cpd_check_launch();
+}
+
+extern "C" int cpd_voxel_pool_max_train_grad(int m, int c, int nsample, int n_rows, const float *grad_out, int grad_out_ld, const uint8_t *arg,
+                                             const int32_t *idx, const float *xyz, const float *new_xyz, const float *w_pos, const float *gamma,
+                                             const float *mean, const float *invstd, const double *moments, float eps, float *grad_features,
+                                             float *grad_w, float *grad_gamma, float *grad_beta, void *workspace,
+                                             size_t workspace_bytes, cpd_stream_t st) {
+    if (m <= 0 || c <= 0 || nsample <= 0 || (long long)m * nsample <= 1 || n_rows < 0 || grad_out_ld < c || !grad_out ||
+        !arg || !idx || !xyz || !new_xyz || !w_pos || !gamma || !mean || !invstd || !moments || (n_rows > 0 && !grad_features) || !grad_w ||
+        !grad_gamma || !grad_beta || !workspace)
+        return CPD_ERR_ARG;
+    if (!pool_train_c_ok(c) || nsample > 255) return CPD_ERR_UNSUPPORTED;
+    const int nb = pool_train_blocks(m, c);
+    if (workspace_bytes < (size_t)nb * 5 * c * sizeof(double)) return CPD_ERR_WORKSPACE;
+    hipStream_t s = cpd_s(st);
+    if (n_rows > 0) CPD_HIP_TRY(hipMemsetAsync(grad_features, 0, (size_t)n_rows * c * sizeof(float), s));
+    double *part = static_cast<double *>(workspace);
+    cpd_launch_log_note("voxel_pool_max_train_grad_kernel");
+#define CPD_POOL_GRAD(C) pool_train_grad_kernel<C><<<nb, 256, 0, s>>>(m, nsample, n_rows, grad_out, grad_out_ld, arg, idx, xyz, new_xyz, w_pos, mean, \
+                                                                     invstd, grad_features, c, part)
+    if (c == 16) CPD_POOL_GRAD(16); else if (c == 32) CPD_POOL_GRAD(32); else CPD_POOL_GRAD(64);
+#undef CPD_POOL_GRAD
+    pool_train_grad_final_kernel<<<c, 256, 0, s>>>(part, nb, c, (double)m * (double)nsample, w_pos, gamma, moments, eps, grad_w, grad_gamma,
+                                                   grad_beta);
     return cpd_check_launch();
 }

@@ -13,7 +13,9 @@ In eval mode (BatchNorm folded) the per-voxel MLP (mlps_in) and the output MLP
 (mlps_out) are 1x1 `cpd_gather_conv` GEMMs; grouping, position encoding, ReLU and max-pool are one
 fused kernel (`cpd_voxel_pool_max`), so the (M, C, nsample) grouped tensors of the reference are
 never materialised. In training mode the module follows the reference's sequence with the differentiable
-`GroupingOperation` (`cpd_group_points` / `cpd_group_points_grad`); see cpd_amd/roi_head_train.py. The neighbour query can use the sparse tensor's own site index
+`GroupingOperation` (`cpd_group_points` / `cpd_group_points_grad`); see cpd_amd/roi_head_train.py. With `fused_train` on, training
+fuses the same span as well (`cpd_voxel_pool_moments` / `cpd_voxel_pool_max_train` / `cpd_voxel_pool_max_train_grad`): the
+position branch is linear, so its batch statistics and BatchNorm backward come from the moments of the neighbour offsets. The neighbour query can use the sparse tensor's own site index
 (`cpd_voxel_query_index`) instead of a dense (B,Z,Y,X) volume.
 """
 import ctypes
@@ -67,6 +69,15 @@ def voxel_query(max_range, radius, nsample, xyz, new_xyz, new_coords, point_indi
     (an ops.SiteIndex of the sparse tensor; whether its ranks are row ids or go through its permutation is recorded in the
     index buffer itself and read on the device). `grid` = cell_geometry(...) with an index: xyz ARE the cells' centres
     (get_voxel_centers), and the kernel computes them instead of loading them."""
+    idx = voxel_query_raw(max_range, radius, nsample, xyz, new_xyz, new_coords, point_indices, index, grid)
+    empty = idx[:, 0] == -1
+    idx[empty] = 0
+    return idx, empty
+
+
+def voxel_query_raw(max_range, radius, nsample, xyz, new_xyz, new_coords, point_indices=None, index=None, grid=None):
+    """The query kernel's own output: idx [M, nsample] i32 of GLOBAL rows, idx[m, 0] == -1 for an empty ball (its other slots 0), the
+    slots behind the last hit pre-filled with the first -- what the fused pooling kernels take."""
     assert xyz.is_contiguous() and new_xyz.is_contiguous() and new_coords.is_contiguous()
     m = new_coords.shape[0]
     idx = torch.zeros((m, nsample), dtype=torch.int32, device=xyz.device)
@@ -78,9 +89,7 @@ def voxel_query(max_range, radius, nsample, xyz, new_xyz, new_coords, point_indi
         b, z, y, x = point_indices.shape
         check(lib().cpd_voxel_query(m, z, y, x, int(nsample), float(radius), zr, yr, xr, ptr(new_xyz), ptr(xyz), ptr(new_coords),
                                     ptr(point_indices), ptr(idx), stream()), "cpd_voxel_query")
-    empty = idx[:, 0] == -1
-    idx[empty] = 0
-    return idx, empty
+    return idx
 
 
 def grouping_operation(features, features_batch_cnt, idx, idx_batch_cnt):
@@ -144,6 +153,91 @@ def voxel_pool_max(features_in, xyz, new_xyz, idx_raw, w_pos, b_pos):
     return out
 
 
+POOL_TRAIN_CHANNELS = (16, 32, 64)          # what cpd_voxel_pool_max_train (and the eval kernel) is instantiated for
+
+
+def voxel_pool_max_train(features_in, xyz, new_xyz, idx_raw, w_pos, gamma, beta, running_mean, running_var, eps, momentum):
+    """cpd_voxel_pool_moments + cpd_voxel_pool_max_train: grouping + position conv + BatchNorm2d on batch statistics + ReLU + max over
+    the samples (voxel_pool_modules.py:96-117) without an (M, C, nsample) tensor. features_in [N, C] (rows may be strided), w_pos [C, 3],
+    idx_raw as voxel_query_raw gives it; running_mean / running_var are updated in place. Returns (out [M, C], arg [M, C] uint8 = the
+    sample attaining the maximum, 255 = cut off by the ReLU, mean [C], invstd [C], moments [9] float64)."""
+    m, ns = idx_raw.shape
+    c = features_in.shape[1]
+    dev = features_in.device
+    assert features_in.stride(1) == 1 and xyz.is_contiguous() and new_xyz.is_contiguous() and idx_raw.is_contiguous()
+    assert w_pos.shape == (c, 3) and w_pos.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()
+    ws = torch.empty(lib().cpd_voxel_pool_train_workspace_bytes(m, c, ns), dtype=torch.uint8, device=dev)
+    moments = torch.empty(9, dtype=torch.float64, device=dev)
+    check(lib().cpd_voxel_pool_moments(m, ns, xyz.shape[0], ptr(xyz), ptr(new_xyz), ptr(idx_raw), ptr(moments), ptr(ws), ws.numel(), stream()),
+          "cpd_voxel_pool_moments")
+    out = torch.empty((m, c), dtype=torch.float32, device=dev)
+    arg = torch.empty((m, c), dtype=torch.uint8, device=dev)
+    mean, invstd = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
+    check(lib().cpd_voxel_pool_max_train(m, c, ns, xyz.shape[0], _p(features_in), features_in.stride(0), ptr(xyz), ptr(new_xyz), ptr(idx_raw),
+                                         ptr(w_pos), ptr(gamma), ptr(beta), ptr(moments), float(eps), float(momentum), _p(running_mean),
+                                         _p(running_var), ptr(out), out.stride(0), ptr(arg), ptr(mean), ptr(invstd), stream()),
+          "cpd_voxel_pool_max_train")
+    return out, arg, mean, invstd, moments
+
+
+def voxel_pool_max_train_grad(grad_out, arg, idx_raw, xyz, new_xyz, w_pos, gamma, mean, invstd, moments, eps, n_rows):
+    """cpd_voxel_pool_max_train_grad -> (d features_in [n_rows, C] by float atomics, d w_pos [C, 3], d gamma [C], d beta [C]; the last
+    three from float64 sums in a fixed order)."""
+    m, ns = idx_raw.shape
+    c = arg.shape[1]
+    dev = arg.device
+    assert grad_out.stride(1) == 1
+    ws = torch.empty(lib().cpd_voxel_pool_train_workspace_bytes(m, c, ns), dtype=torch.uint8, device=dev)
+    dfin = torch.empty((n_rows, c), dtype=torch.float32, device=dev)
+    dw = torch.empty((c, 3), dtype=torch.float32, device=dev)
+    dgamma, dbeta = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
+    check(lib().cpd_voxel_pool_max_train_grad(m, c, ns, n_rows, _p(grad_out), grad_out.stride(0), ptr(arg), ptr(idx_raw), ptr(xyz), ptr(new_xyz),
+                                              ptr(w_pos), ptr(gamma), ptr(mean), ptr(invstd), ptr(moments), float(eps), _p(dfin), ptr(dw),
+                                              ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream()), "cpd_voxel_pool_max_train_grad")
+    return dfin, dw, dgamma, dbeta
+
+
+class VoxelPoolMaxTrain(torch.autograd.Function):
+    """The fused pooling of one scale in training (voxel_pool_max_train / voxel_pool_max_train_grad): differentiable in features_in and in
+    the position branch's parameters (conv weight [C, 3, 1, 1], BatchNorm weight and bias); xyz / new_xyz get no gradient (the RoIs are
+    detached). The running statistics are updated in place by the forward; num_batches_tracked is the caller's."""
+
+    @staticmethod
+    def forward(ctx, features_in, conv_weight, gamma, beta, xyz, new_xyz, idx_raw, running_mean, running_var, eps, momentum):
+        fin = features_in.detach().float()
+        if fin.stride(1) != 1:
+            fin = fin.contiguous()
+        c = fin.shape[1]
+        w = conv_weight.detach().reshape(c, 3).contiguous().float()
+        g, b = gamma.detach().contiguous().float(), beta.detach().contiguous().float()
+        out, arg, mean, invstd, moments = voxel_pool_max_train(fin, xyz, new_xyz, idx_raw, w, g, b, running_mean, running_var, eps, momentum)
+        ctx.save_for_backward(arg, idx_raw, xyz, new_xyz, w, g, mean, invstd, moments)
+        ctx.eps, ctx.n_rows, ctx.w_shape = float(eps), fin.shape[0], conv_weight.shape
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        arg, idx_raw, xyz, new_xyz, w, g, mean, invstd, moments = ctx.saved_tensors
+        grad_out = grad_out.float()
+        if grad_out.stride(1) != 1:
+            grad_out = grad_out.contiguous()
+        dfin, dw, dgamma, dbeta = voxel_pool_max_train_grad(grad_out, arg, idx_raw, xyz, new_xyz, w, g, mean, invstd, moments, ctx.eps,
+                                                            ctx.n_rows)
+        return dfin, dw.view(ctx.w_shape), dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def set_fused_train(model, on=True):
+    """Flip `fused_train` on every NeighborVoxelSAModuleMSG of `model` (both pooling stacks of VoxelRCNNProtoHead, VoxelRCNNHead's);
+    returns how many there were."""
+    n = 0
+    for mod in model.modules():
+        if isinstance(mod, NeighborVoxelSAModuleMSG):
+            mod.fused_train = bool(on)
+            n += 1
+    return n
+
+
 def _fold(bn):
     scale = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
     return scale, bn.bias.detach() - bn.running_mean * scale
@@ -153,7 +247,12 @@ class NeighborVoxelSAModuleMSG(nn.Module):
     """State-dict compatible with the reference module (mlps_in / mlps_pos / mlps_out). Eval mode: BatchNorm folded, three
     launches per scale (see the module docstring). Training mode: the reference's own sequence (voxel_pool_modules.py:86-128) --
     torch Conv / BatchNorm modules with batch statistics on the device, the neighbour query and the differentiable grouping
-    (`GroupingOperation`) on the C-ABI kernels --, so gradients reach the MLPs and, through `features`, the sparse backbone."""
+    (`GroupingOperation`) on the C-ABI kernels --, so gradients reach the MLPs and, through `features`, the sparse backbone.
+    `fused_train` (default False; set_fused_train flips it on a whole model): training runs grouping + mlps_pos + ReLU + max-pool of a
+    scale as ONE differentiable op (VoxelPoolMaxTrain) that stores no (M, C, nsample) tensor; parameters and state-dict are the same.
+    A scale the fused kernels do not cover -- the cases in which HipBatchNorm2d itself leaves its kernel path (BatchNorm in eval mode,
+    without running statistics, affine or momentum, a single slot), a width other than 16 / 32 / 64, coordinates that require a
+    gradient -- takes the module sequence as before."""
 
     def __init__(self, *, query_ranges, radii, nsamples, mlps, use_xyz=True, pool_method="max_pool"):
         super().__init__()
@@ -172,6 +271,18 @@ class NeighborVoxelSAModuleMSG(nn.Module):
             if isinstance(m, (nn.Conv2d, nn.Conv1d)):
                 nn.init.kaiming_normal_(m.weight)
         self._packed = None
+        self.fused_train = False
+
+    def _fused_scale(self, k, xyz, new_xyz):
+        """whether scale k takes the fused training op (the conditions of autograd_ops._bn_rows' kernel path, and the kernels' own)"""
+        conv, bn = self.mlps_pos[k][0], self.mlps_pos[k][1]
+        return bool(self.fused_train and bn.training and bn.track_running_stats and bn.affine and bn.momentum is not None
+                    and xyz.is_cuda and new_xyz.shape[0] * int(self.nsamples[k]) > 1 and int(self.nsamples[k]) <= 255
+                    and conv.out_channels in POOL_TRAIN_CHANNELS and not xyz.requires_grad and not new_xyz.requires_grad)
+
+    def fused_train_ready(self, xyz, new_xyz):
+        """True when a training forward on these coordinates runs EVERY scale fused: the per-sample row counts are then not needed"""
+        return self.training and all(self._fused_scale(k, xyz, new_xyz) for k in range(len(self.nsamples)))
 
     def _pack(self):
         pk = []
@@ -194,6 +305,16 @@ class NeighborVoxelSAModuleMSG(nn.Module):
         for k in range(len(self.nsamples)):
             fin = self.mlps_in[k](features.permute(1, 0).unsqueeze(0))                       # (1, C1, N)
             fin = fin.permute(0, 2, 1).contiguous().view(-1, fin.shape[1])                   # (N, C1)
+            if self._fused_scale(k, xyz, new_xyz):
+                conv, bn = self.mlps_pos[k][0], self.mlps_pos[k][1]
+                idx = voxel_query_raw(self.query_ranges[k], self.radii[k], self.nsamples[k], xyz, new_xyz, new_coords, voxel2point_indices, index)
+                x = VoxelPoolMaxTrain.apply(fin, conv.weight, bn.weight, bn.bias, xyz, new_xyz, idx, bn.running_mean, bn.running_var, bn.eps,
+                                            bn.momentum)
+                with torch.no_grad():
+                    bn.num_batches_tracked += 1
+                outs.append(self.mlps_out[k](x.t().unsqueeze(0)).squeeze(0).permute(1, 0))
+                continue
+            assert xyz_batch_cnt is not None, "the module sequence groups per sample: pass xyz_batch_cnt"
             gf, gx, empty = voxel_query_and_grouping(self.query_ranges[k], self.radii[k], self.nsamples[k], new_coords, xyz,
                                                      xyz_batch_cnt, new_xyz, new_xyz_batch_cnt, fin, voxel2point_indices, index)
             keep = (~empty).to(gf.dtype)[:, None, None]
@@ -332,8 +453,9 @@ def roi_grid_pool(rois, levels, strides, pool_layers, grid_size, voxel_size, poi
             feats = feats.contiguous()
         stride = strides[name]
         xyz = get_voxel_centers(coords[:, 1:4], stride, voxel_size, point_cloud_range).contiguous()
-        # (per-sample row counts: the training branch's grouping needs them; the fused eval path does not -- and bincount reads back)
-        cnt = None if fused else torch.bincount(coords[:, 0].long(), minlength=batch_size).int()
+        # (per-sample row counts: the training branch's grouping needs them; the fused eval path and the fused training op take global
+        # rows and do not -- and bincount reads back)
+        cnt = None if fused or layer.fused_train_ready(xyz, grid_flat) else torch.bincount(coords[:, 0].long(), minlength=batch_size).int()
         cur = cells[int(stride)]
         index = indexes.get(name) if indexes else None
         v2p = None if index is not None else generate_voxel2pinds(coords, batch_size, shape)

@@ -701,6 +701,37 @@ int cpd_voxel_pool_max_mlp_ranged(int m, int c, int nsample, const float *featur
                                   const float *xyz, const float *new_xyz, const int32_t *idx, const float *w_pos,
                                   const float *b_pos, const float *w_out, const float *t_out, int c_out, int relu,
                                   float *out, int out_ld, uint32_t *out_absmax, cpd_stream_t stream);
+/* The same pooling for TRAINING, fused and differentiable (voxel_pool_modules.py:96-117 with mlps_pos = Conv2d(3, c, bias=False) +
+ * BatchNorm2d on batch statistics): no (m, c, nsample) tensor is stored. With p[m][s] = xyz[idx[m][s]] - new_xyz[m] (0 for an empty
+ * ball, idx[m][0] < 0) and n = m * nsample slots -- empty balls and pre-filled duplicates count, as in the reference -- the position
+ * branch's batch statistics follow from the moments of p. Row conventions as cpd_voxel_pool_max (features_ld, out_ld, global idx);
+ * every gather is guarded: a row outside [0, n_rows) counts as an empty slot. c = 16, 32 or 64 and nsample <= 255, else
+ * CPD_ERR_UNSUPPORTED; m * nsample <= 1 is CPD_ERR_ARG (no batch statistics).
+ * Workspace of the moments and the gradient entry (device memory, 256-byte aligned): */
+size_t cpd_voxel_pool_train_workspace_bytes(int m, int c, int nsample);
+/* moments [9] (device float64) = sum p (x y z), sum p p^T (xx xy xz yy yz zz) over all slots (voxel_pool_modules.py:96-117: the input
+ * of mlps_pos), accumulated in float64 in a fixed order: bitwise repeatable. */
+int cpd_voxel_pool_moments(int m, int nsample, int n_rows, const float *xyz, const float *new_xyz, const int32_t *idx,
+                           double *moments, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+/* Forward (voxel_pool_modules.py:96-117). Per channel ch with w = w_pos[ch] (w_pos [c, 3] = the Conv2d weight):
+ *   mean = w . S1 / n, var = w (S2 / n - S1 S1^T / n^2) w^T (biased), invstd = 1 / sqrt(var + eps)       -> mean [c], invstd [c]
+ *   running_mean / running_var [c] (may both be NULL) updated in place with `momentum` and the unbiased variance, torch's rule
+ *   out[m][ch] = max_s relu(keep[m] * features_in[idx[m][s]][ch] + gamma[ch] * ((w . p[m][s]) - mean) * invstd + beta[ch])
+ *   arg[m][ch] (uint8, [m, c]) = the first s attaining the maximum, or 255 where out == 0 (no gradient: torch's ReLU rule). */
+int cpd_voxel_pool_max_train(int m, int c, int nsample, int n_rows, const float *features_in, int features_ld, const float *xyz,
+                             const float *new_xyz, const int32_t *idx, const float *w_pos, const float *gamma, const float *beta,
+                             const double *moments, float eps, float momentum, float *running_mean, float *running_var,
+                             float *out, int out_ld, uint8_t *arg, float *mean, float *invstd, cpd_stream_t stream);
+/* Backward (voxel_pool_modules.py:96-117). With G = grad_out where arg != 255, else 0, and p*, zhat* the values at arg:
+ *   grad_features [n_rows, c] (zeroed here) [idx[m][arg]][ch] += keep * G          (float atomics, as cpd_group_points_grad)
+ *   grad_beta = sum G, grad_gamma = sum G zhat*,
+ *   grad_w [c, 3] = gamma invstd [ sum G p* - (sum G / n) S1 - (sum G zhat* / n) invstd (S2 w - mean S1) ]
+ * the three sums in float64 in a fixed order (bitwise repeatable). No gradient reaches xyz / new_xyz. */
+int cpd_voxel_pool_max_train_grad(int m, int c, int nsample, int n_rows, const float *grad_out, int grad_out_ld, const uint8_t *arg,
+                                  const int32_t *idx, const float *xyz, const float *new_xyz, const float *w_pos, const float *gamma,
+                                  const float *mean, const float *invstd, const double *moments, float eps, float *grad_features,
+                                  float *grad_w, float *grad_gamma, float *grad_beta, void *workspace, size_t workspace_bytes,
+                                  cpd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataloader pre-filter on the device.

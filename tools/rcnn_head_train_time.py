@@ -4,8 +4,11 @@
     restatement rcnn_head_loss_torch (+ its .item() read-backs), at the shipped size B = 2, ROI_PER_IMAGE = 150, with backward;
   * one head training step: forward (proposal layer, sampling, pooling, FC stacks) + get_loss + backward, the shipped ROI_HEAD of
     voxel_rcnn_dbscan_single_train.yaml (GRID_SIZE 6; x_conv3 / x_conv4 with two radii each: four pooling scales) on synthetic
-    sparse levels and proposals.
-Median of cuda-event-timed repetitions after warm-up. Prints one JSON line.  Usage: python tools/rcnn_head_train_time.py"""
+    sparse levels and proposals; the same step split into phases by events (proposal layer, target sampling, pooling forward, FC
+    stacks, loss, backward) and its peak allocated memory. --fused-pool turns NeighborVoxelSAModuleMSG.fused_train on
+    (roi_pool.set_fused_train): pooling through cpd_voxel_pool_max_train instead of the module sequence.
+Median of cuda-event-timed repetitions after warm-up. Prints one JSON line.  Usage: python tools/rcnn_head_train_time.py [--fused-pool]"""
+import argparse
 import json
 import os
 import sys
@@ -45,7 +48,11 @@ def loss_rows(n, seed=0):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--fused-pool", action="store_true", help="train the pooling through the fused op (fused_train on every pooling module)")
+    opt = ap.parse_args()
     from cpd_amd import models, roi_pool
+    from cpd_amd.roi_head_train import assign_targets
     from cpd_amd.roi_head_train import rcnn_head_loss, rcnn_head_loss_torch
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0)}
@@ -78,6 +85,9 @@ def main():
     torch.manual_seed(0)
     head = roi_pool.VoxelRCNNHead(chans, cfg, point_cloud_range=pcr, voxel_size=vs, num_class=1).cuda().train()
     head.init_weights()
+    out["fused_pool"] = bool(opt.fused_pool)
+    if opt.fused_pool:
+        roi_pool.set_fused_train(head)
     rng = np.random.default_rng(0)
     B, n_gt = 2, 40
     gt = np.zeros((B, n_gt, 8), np.float32)
@@ -99,15 +109,54 @@ def main():
         levels[name] = types.SimpleNamespace(indices=idx, features=f, spatial_shape=shp, batch_size=B)
     gt_t, boxes_t, scores_t = torch.from_numpy(gt).cuda(), torch.from_numpy(boxes).cuda(), torch.from_numpy(scores).cuda()
 
+    def batch():
+        return {"batch_size": B, "batch_box_preds": boxes_t, "batch_cls_preds": scores_t, "gt_boxes": gt_t, "multi_scale_3d_features": levels,
+                "multi_scale_3d_strides": {"x_conv3": 4, "x_conv4": 8}}
+
     def step():
-        bd = {"batch_size": B, "batch_box_preds": boxes_t, "batch_cls_preds": scores_t, "gt_boxes": gt_t, "multi_scale_3d_features": levels,
-              "multi_scale_3d_strides": {"x_conv3": 4, "x_conv4": 8}}
+        bd = batch()
         head(bd)
         loss, _ = head.get_loss()
         head.zero_grad(set_to_none=True)
         loss.backward()
     out["head_step_rois"] = B * per
     out["head_step_ms"] = timed(step, reps=20, warmup=3)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    torch.cuda.synchronize()
+    out["head_step_peak_mb"] = torch.cuda.max_memory_allocated() / 2 ** 20
+
+    # the same step, VoxelRCNNHead.forward's training branch statement by statement with an event between the phases
+    names = ("proposal_layer", "target_sampling", "pooling_forward", "fc_stacks", "loss", "backward")
+
+    def phases():
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        bd = batch()
+        marks[0].record()
+        head._fc = None
+        head._proposals(bd, "TRAIN")
+        marks[1].record()
+        targets = assign_targets(head.proposal_target_layer, bd)
+        bd["rois"], bd["roi_labels"] = targets["rois"], targets["roi_labels"]
+        marks[2].record()
+        pooled = head._pool(bd)
+        marks[3].record()
+        shared = head.shared_fc_layers(pooled.reshape(pooled.shape[0], -1))
+        targets.update(rcnn_cls=head.cls_layers(shared), rcnn_reg=head.reg_layers(shared))
+        head.forward_ret_dict = targets
+        marks[4].record()
+        loss, _ = head.get_loss()
+        marks[5].record()
+        head.zero_grad(set_to_none=True)
+        loss.backward()
+        marks[6].record()
+        marks[6].synchronize()
+        return [marks[i].elapsed_time(marks[i + 1]) for i in range(len(names))]
+    for _ in range(3):
+        phases()
+    runs = np.array([phases() for _ in range(20)])
+    out["head_step_phases_ms"] = {k: float(v) for k, v in zip(names, np.median(runs, axis=0))}
     print(json.dumps(out))
 
 
