@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import autograd_ops, iou3d_nms_utils, layer_table, ops, train_ops
+from . import autograd_ops, iou3d_nms_utils, layer_table, ops, recall, train_ops
 from . import spconv as _spconv_pkg
 from .spconv import pytorch as spconv
 from .spconv.pytorch import conv as _spc
@@ -882,7 +882,24 @@ class CenterPoint(nn.Module):
         if self.training:
             loss_rpn, tb_dict = self.dense_head.get_loss()
             return {"loss": loss_rpn}, dict(loss_rpn=loss_rpn.item(), **tb_dict), {}
-        return batch_dict["final_box_dicts"], {}
+        return self.post_processing(batch_dict)
+
+    def post_processing(self, batch_dict):
+        """centerpoint.py:36-50: the dense head's final boxes and the batch's recall record."""
+        preds = batch_dict["final_box_dicts"]
+        return preds, self._recall_dict(batch_dict, [d["pred_boxes"] for d in preds])
+
+    generate_recall_record = staticmethod(recall.generate_recall_record)      # detector3d_template.py:344-386
+
+    def _recall_dict(self, batch_dict, boxes_per_frame):
+        """The recall_dict of post_processing (detector3d_template.py:326-330, centerpoint.py:36-50) for the whole batch: one
+        cpd_recall_record launch, one read-back; {} without `gt_boxes`, as generate_recall_record returns then (l.346-347)."""
+        if "gt_boxes" not in batch_dict:
+            return {}
+        pp = self.model_cfg.get("POST_PROCESSING") or {}
+        rec = recall.RecallRecord(pp.get("RECALL_THRESH_LIST", recall.DEFAULT_THRESH_LIST), device=boxes_per_frame[0].device)
+        rec.update(list(boxes_per_frame), None, None, batch_dict["gt_boxes"], rois=batch_dict.get("rois"))
+        return rec.as_dict()
 
     FAST_EVAL_STICKY_STEPS = 16
 
@@ -1114,7 +1131,7 @@ class VoxelRCNN(CenterPoint):
             if pp.get("WBF", False):
                 rec["WBF"] = True
             pred_dicts.append(rec)
-        return pred_dicts, {}
+        return pred_dicts, self._recall_dict(batch_dict, [d["pred_boxes"] for d in pred_dicts])
 
     def forward(self, batch_dict):
         batch_dict = self._run_modules(batch_dict)          # (fast eval: the first stage inside the optimistic range pass, CenterPoint._run_modules;

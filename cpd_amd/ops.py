@@ -752,6 +752,28 @@ def boxes_iou3d(a, b):
     return _pairwise(lib().cpd_boxes_iou3d, "cpd_boxes_iou3d", a, b)
 
 
+def recall_record(pred, pred_start, pred_count, gt, thresh, counters, rois=None, roi_start=None, roi_count=None,
+                  best_rcnn=None, best_roi=None, n_gt=None):
+    """cpd_recall_record: the recall counters of Detector3DTemplate.generate_recall_record for all frames of `gt` [B, M, ld] in one
+    launch, queued on the current stream (no host wait). `pred` / `rois`: float32 rows [..., ld >= 7] on the device -- a padded
+    [B, cap, ld] block or a concatenation [R, ld]; `*_start` / `*_count` int32 [B] on the device name each frame's rows in them.
+    `counters` int64 [1 + 2 * len(thresh)] on the device is ADDED to. Optional outputs: best_rcnn / best_roi float32 [B, M], n_gt
+    int32 [B]."""
+    _need_cuda(gt, "gt_boxes")
+    assert gt.dim() == 3 and gt.dtype == torch.float32 and pred.dtype == torch.float32 and pred.shape[-1] >= 7
+    assert counters.dtype == torch.int64 and counters.numel() == 1 + 2 * len(thresh)
+    batch, cap, ld = gt.shape
+    for t in (pred_start, pred_count, roi_start, roi_count, n_gt):
+        assert t is None or (t.dtype == torch.int32 and t.numel() == batch)
+    for t in (best_rcnn, best_roi):
+        assert t is None or (t.dtype == torch.float32 and t.numel() == batch * cap)
+    assert rois is None or (rois.dtype == torch.float32 and rois.shape[-1] >= 7)
+    check(lib().cpd_recall_record(ptr(pred), pred.shape[-1], ptr(pred_start), ptr(pred_count), ptr(rois),
+                                  rois.shape[-1] if rois is not None else 0, ptr(roi_start), ptr(roi_count), ptr(gt), batch, cap, ld,
+                                  farr(thresh), len(thresh), ptr(counters), ptr(best_rcnn), ptr(best_roi), ptr(n_gt), stream()),
+          "cpd_recall_record")
+
+
 def nms(boxes_sorted, thresh, normal=False, sync=True):
     """boxes sorted by descending score. Returns kept row ids (device i64 [num]) (sync=True) or
     (keep [n], num_keep [1]) device tensors."""

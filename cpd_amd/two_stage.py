@@ -59,7 +59,9 @@ class VoxelRCNNEngine:
             raise NotImplementedError("post-processing variant not selected by the shipped CPD configs")
 
     @torch.no_grad()
-    def forward(self, points_list: List[torch.Tensor], return_intermediates=False):
+    def forward(self, points_list: List[torch.Tensor], return_intermediates=False, gt_boxes=None, recall=None):
+        """`gt_boxes` [batch, M, ld >= 7] with `recall` (a cpd_amd.recall.RecallRecord): the step also adds its frames to the recall
+        record (generate_recall_record, detector3d_template.py:344-386) -- one more launch, queued before the step's read-back."""
         if isinstance(points_list, torch.Tensor):
             points_list = [points_list]
         batch = len(points_list)
@@ -96,6 +98,8 @@ class VoxelRCNNEngine:
         keep, num_keep = ops.nms_batch(sboxes, n_ok, float(nms["NMS_THRESH"]))
         post = min(int(nms["NMS_POST_MAXSIZE"]), n_roi)
         fb, fs, fl, fn, blk = ops.select_boxes(sboxes, ranked, slabels, keep, num_keep, post, label_offset=0, packed=True)
+        if recall is not None and gt_boxes is not None:                  # the padded final block and its device counts; every RoI slot
+            recall.update(fb, None, fn, gt_boxes, rois=rois)
         if self.host_results:                                            # counts + boxes + scores + labels: one block, one copy
             hdr, fb, fs, fl = ops.unpack_boxes(blk.cpu(), blk._cpd_layout)
             ns = hdr.tolist()

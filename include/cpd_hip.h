@@ -403,6 +403,24 @@ int cpd_select_boxes(const float *boxes, const float *scores, const int32_t *lab
                      const int64_t *keep, const int32_t *num_keep, int batch, int capacity,
                      int post_max, int label_offset, float *out_boxes, float *out_scores,
                      int64_t *out_labels, int32_t *out_n, cpd_stream_t stream);
+/* generate_recall_record (cpd/models/detectors/detector3d_template.py:344-386; called per frame from post_processing, l.326-330, and
+ * cpd/models/detectors/centerpoint.py:36-50; summed by tools/eval_utils/eval_utils.py:14-21,94-101) for ALL frames of a batch in one
+ * launch, with no host wait. Frame b's final boxes are rows pred_start[b] .. pred_start[b] + pred_count[b] of `pred` (row pitch pred_ld
+ * floats, columns 0:7 read); its RoIs likewise in `rois` (NULL: a one-stage model, the roi counters are left alone). The start / count
+ * arrays are DEVICE int32 [batch]: a padded block (start = b * capacity, counts from the NMS) and a concatenation of per-frame tensors
+ * are addressed alike; every row they name must exist. gt [batch][gt_cap][gt_ld] f32, gt_ld >= 7, columns 0:7 the box: rows 0 .. k of a
+ * frame count, k the last row whose float32 sum over all gt_ld columns is not zero and never less than 0 (l.358-362: an all-zero block
+ * counts one gt; a zero row between real rows counts); gt_cap == 0 counts nothing. thresh: HOST array of n_thresh (1..8) values >= 0.
+ * counters: device int64 [1 + 2 * n_thresh] = gt, roi_<t0> .., rcnn_<t0> ..; ADDED to, never cleared here: a counted gt adds 1 to
+ * rcnn_<t> when the largest boxes_iou3d_gpu value (the expression of cpd_boxes_iou3d) of its column over the frame's final boxes is > t
+ * (strict; no boxes: nothing), and to roi_<t> likewise over the RoIs (zero-padded RoI rows take part: IoU 0). Optional outputs (NULL to
+ * skip): best_rcnn / best_roi [batch][gt_cap] f32 = that largest IoU per counted gt (-1 where the frame has no such boxes), -1 for rows
+ * not counted; n_gt [batch] i32 = rows counted per frame. CPD_ERR_ARG: batch outside 1..65535, gt_ld / pred_ld / roi_ld < 7, n_thresh
+ * outside 1..8, a negative or NaN threshold, a null required pointer. */
+int cpd_recall_record(const float *pred, int pred_ld, const int32_t *pred_start, const int32_t *pred_count,
+                      const float *rois, int roi_ld, const int32_t *roi_start, const int32_t *roi_count,
+                      const float *gt, int batch, int gt_cap, int gt_ld, const float *thresh, int n_thresh,
+                      int64_t *counters, float *best_rcnn, float *best_roi, int32_t *n_gt, cpd_stream_t stream);
 /* boxes_iou_bev_cpu (iou3d_cpu.cpp:232-252): HOST pointers, runs on the calling thread. This is
  * the one CPU entry point the reference extension itself exports (used by the dataloader's
  * gt-sampling, database_sampler.py:445-446); it is product code, not the test oracle.        */
