@@ -91,6 +91,9 @@ SIGNATURES = {
     "cpd_rank_scores": (_I, [_VP, _I, _VP, _VP, _I, _I, _F, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "cpd_select_boxes": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP]),
     "cpd_recall_record": (_I, [_VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _FP, _I, _VP, _VP, _VP, _VP, _VP]),
+    "cpd_wbf_workspace_bytes": (_SZ, [_I]),
+    "cpd_wbf_cluster": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_wbf_cluster_cpu": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     "cpd_boxes_iou_bev_cpu": (_I, [_VP, _I, _VP, _I, _VP]),
     "cpd_col_reduce_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_col_sum": (_I, [_VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),

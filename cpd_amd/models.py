@@ -1063,8 +1063,8 @@ def multi_classes_nms(cls_scores, box_preds, nms_config, score_thresh=None):
 
 def post_process_frame(pp, num_class, box_preds, cls_preds, normalized, label_preds=None, label_mapping=None):
     """One frame of Detector3DTemplate.post_processing (cpd/models/detectors/detector3d_template.py:246-331): every branch of it --
-    MULTI_CLASSES_NMS (single tensor or the multi-head list with `label_mapping`), WBF (score mask only: the fusion itself happens in the
-    evaluation scripts), class-agnostic NMS with OUTPUT_RAW_SCORE. `label_preds`: the RoI / dense-head labels when has_class_labels.
+    MULTI_CLASSES_NMS (single tensor or the multi-head list with `label_mapping`), WBF (score mask only, as in the reference: the fusion of the views'
+    results is cpd_amd.wbf -- merge_frames for the evaluation side, model_compute_WBF for the model-side variant), class-agnostic NMS with OUTPUT_RAW_SCORE. `label_preds`: the RoI / dense-head labels when has_class_labels.
     -> (boxes, scores, labels)"""
     multi = isinstance(cls_preds, (list, tuple))
     src = cls_preds

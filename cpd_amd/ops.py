@@ -774,6 +774,59 @@ def recall_record(pred, pred_start, pred_count, gt, thresh, counters, rois=None,
           "cpd_recall_record")
 
 
+def wbf_workspace_bytes(n):
+    return int(lib().cpd_wbf_workspace_bytes(int(n)))
+
+
+def wbf_cluster(boxes, scores, seg_start, seg_count, seg_thresh, seg_mode, out_boxes=None, out_scores=None, out_count=None,
+                cluster_of=None, workspace=None):
+    """cpd_wbf_cluster: weighted box fusion of all segments in one launch, queued on the current stream (no host wait). boxes [n, 7] /
+    scores [n] float32 on the device, every segment floored and sorted by descending score; seg_start / seg_count / seg_mode int32
+    [S], seg_thresh float32 [S, 2] on the device (include/cpd_hip.h). -> (out_boxes [n, 7], out_scores [n], out_count [S],
+    cluster_of [n]); rows no segment writes are left as they were (fresh tensors: zeros, cluster_of -3)."""
+    _need_cuda(boxes, "boxes")
+    n, s = int(scores.numel()), int(seg_start.numel())
+    dev = boxes.device
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and boxes.numel() == 7 * n
+    assert seg_thresh.dtype == torch.float32 and seg_thresh.numel() == 2 * s
+    for t in (seg_start, seg_count, seg_mode):
+        assert t.dtype == torch.int32 and t.numel() == s
+    if out_boxes is None:
+        out_boxes = torch.zeros((n, 7), dtype=torch.float32, device=dev)
+    if out_scores is None:
+        out_scores = torch.zeros((n,), dtype=torch.float32, device=dev)
+    if out_count is None:
+        out_count = torch.zeros((s,), dtype=torch.int32, device=dev)
+    if cluster_of is None:
+        cluster_of = torch.full((n,), -3, dtype=torch.int32, device=dev)
+    assert out_boxes.dtype == torch.float32 and out_boxes.numel() == 7 * n and out_scores.dtype == torch.float32 and out_scores.numel() == n
+    assert out_count.dtype == torch.int32 and out_count.numel() == s and cluster_of.dtype == torch.int32 and cluster_of.numel() == n
+    need = wbf_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    assert workspace.numel() * workspace.element_size() >= need
+    check(lib().cpd_wbf_cluster(ptr(boxes), ptr(scores), n, ptr(seg_start), ptr(seg_count), ptr(seg_thresh), ptr(seg_mode), s,
+                                ptr(out_boxes), ptr(out_scores), ptr(out_count), ptr(cluster_of), ptr(workspace),
+                                workspace.numel() * workspace.element_size(), stream()), "cpd_wbf_cluster")
+    return out_boxes, out_scores, out_count, cluster_of
+
+
+def wbf_cluster_cpu(boxes, scores, seg_start, seg_count, seg_thresh, seg_mode):
+    """cpd_wbf_cluster_cpu: wbf_cluster's rules on the calling thread. HOST tensors (float32 / int32, shapes as wbf_cluster's) ->
+    (out_boxes [n, 7], out_scores [n], out_count [S], cluster_of [n]) host tensors; rows no segment writes hold zeros / -3."""
+    n, s = int(scores.numel()), int(seg_start.numel())
+    for t in (boxes, scores, seg_thresh):
+        assert not t.is_cuda and t.dtype == torch.float32
+    for t in (seg_start, seg_count, seg_mode):
+        assert not t.is_cuda and t.dtype == torch.int32 and t.numel() == s
+    assert boxes.numel() == 7 * n and seg_thresh.numel() == 2 * s
+    out_boxes, out_scores = torch.zeros((n, 7), dtype=torch.float32), torch.zeros((n,), dtype=torch.float32)
+    out_count, cluster_of = torch.zeros((s,), dtype=torch.int32), torch.full((n,), -3, dtype=torch.int32)
+    check(lib().cpd_wbf_cluster_cpu(ptr(boxes), ptr(scores), n, ptr(seg_start), ptr(seg_count), ptr(seg_thresh), ptr(seg_mode), s,
+                                    ptr(out_boxes), ptr(out_scores), ptr(out_count), ptr(cluster_of)), "cpd_wbf_cluster_cpu")
+    return out_boxes, out_scores, out_count, cluster_of
+
+
 def nms(boxes_sorted, thresh, normal=False, sync=True):
     """boxes sorted by descending score. Returns kept row ids (device i64 [num]) (sync=True) or
     (keep [n], num_keep [1]) device tensors."""

@@ -421,6 +421,37 @@ int cpd_recall_record(const float *pred, int pred_ld, const int32_t *pred_start,
                       const float *rois, int roi_ld, const int32_t *roi_start, const int32_t *roi_count,
                       const float *gt, int batch, int gt_cap, int gt_ld, const float *thresh, int n_thresh,
                       int64_t *counters, float *best_rcnn, float *best_roi, int32_t *n_gt, cpd_stream_t stream);
+/* Weighted box fusion of test-time-augmentation views: DetectionsMerger.compute_WBF (cpd/datasets/kitti/kitti_object_eval_python/
+ * merge_detections.py:110-181; the same text as compute_WBF of merge_detections_tracking.py:121-191) and model_nms_utils.compute_WBF
+ * (cpd/models/model_utils/model_nms_utils.py:14-113), for ALL segments of a batch in one launch with no host wait. A segment is the
+ * boxes of one frame and one class after the score floor, by descending score: rows seg_start[s] .. seg_start[s] + seg_count[s] of
+ * boxes [n][7] / scores [n] (DEVICE int32 [n_seg]; segments must not overlap, every row they name must exist; at most
+ * CPD_WBF_MAX_SEGMENT rows each). seg_thresh [n_seg][2] f32 = iou_thresh, iou_thresh2 (the second read by the model variant only);
+ * seg_mode [n_seg] i32 = 0 (WBF-mean) or a sum of CPD_WBF_MAX (type 'max'), CPD_WBF_MODEL (the model_nms_utils rules),
+ * CPD_WBF_NO_RETAIN (retain_low=False; model variant only). One workgroup per segment takes the boxes in order: the lanes take the
+ * rotated BEV IoU (the expression of cpd_boxes_iou_bev_cpu) of the box with every cluster so far, a block reduction yields the
+ * largest IoU and the lowest cluster index that attains it (np.argmax), one thread applies the rule. Headings are folded first
+ * (limit_period(0.5, 2 pi) / model_nms_utils.limit); the inputs are not written.
+ * Outputs: out_boxes [n][7] / out_scores [n]: segment s's results in rows seg_start[s] .. + out_count[s], clusters in creation order
+ * (model variant: the boxes emitted on their own first, in input order); rows beyond are left alone. out_count [n_seg] i32; -1 for a
+ * segment that is out of range or longer than CPD_WBF_MAX_SEGMENT (nothing else is written for it). cluster_of [n] i32: for every box of
+ * a segment the cluster it joined (creation index), -1 dropped, -2 emitted on its own.
+ * Workspace: cpd_wbf_workspace_bytes(n); the state of the first CPD_WBF_LDS_CLUSTERS clusters of a segment lives in LDS, the rest there. */
+#define CPD_WBF_MAX 1
+#define CPD_WBF_MODEL 2
+#define CPD_WBF_NO_RETAIN 4
+#define CPD_WBF_MAX_SEGMENT 8192
+#define CPD_WBF_LDS_CLUSTERS 512
+#define CPD_WBF_BLOCK 256
+size_t cpd_wbf_workspace_bytes(int n);
+int cpd_wbf_cluster(const float *boxes, const float *scores, int n, const int32_t *seg_start, const int32_t *seg_count,
+                    const float *seg_thresh, const int32_t *seg_mode, int n_seg, float *out_boxes, float *out_scores,
+                    int32_t *out_count, int32_t *cluster_of, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+/* The same clustering on the calling thread, HOST pointers throughout (the rules of csrc/wbf_rules.h compiled for the host; like
+ * cpd_boxes_iou_bev_cpu it needs no device): same arguments without workspace and stream, same outputs. */
+int cpd_wbf_cluster_cpu(const float *boxes, const float *scores, int n, const int32_t *seg_start, const int32_t *seg_count,
+                        const float *seg_thresh, const int32_t *seg_mode, int n_seg, float *out_boxes, float *out_scores,
+                        int32_t *out_count, int32_t *cluster_of);
 /* boxes_iou_bev_cpu (iou3d_cpu.cpp:232-252): HOST pointers, runs on the calling thread. This is
  * the one CPU entry point the reference extension itself exports (used by the dataloader's
  * gt-sampling, database_sampler.py:445-446); it is product code, not the test oracle.        */
