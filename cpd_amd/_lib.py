@@ -94,6 +94,9 @@ SIGNATURES = {
     "cpd_wbf_workspace_bytes": (_SZ, [_I]),
     "cpd_wbf_cluster": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_wbf_cluster_cpu": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    "cpd_kitti_fov_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_kitti_fov_points": (_I, [_VP, _I, _I, _VP, _I, _I, _VP, _D, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_kitti_export": (_I, [_VP, _VP, _VP, _I, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cpd_boxes_iou_bev_cpu": (_I, [_VP, _I, _VP, _I, _VP]),
     "cpd_col_reduce_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_col_sum": (_I, [_VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),

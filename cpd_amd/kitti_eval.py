@@ -3,7 +3,7 @@ cpd/datasets/kitti/kitti_object_eval_python/eval.py (and its rotate_iou.py), wit
 
 Same public surface and the same return values: get_official_eval_result(gt_annos, dt_annos, current_classes,
 PR_detail_dict=None) -> (result string, ret_dict), and the helpers it is built from. Inputs are kitti_common
-annotation dicts of numpy arrays, as Kitti2WaymoDataset builds them.
+annotation dicts of numpy arrays, as Kitti2WaymoDataset builds them (cpd_amd.kitti2waymo.generate_prediction_dicts makes the detections' side).
 
 Where the work runs:
   * overlaps (image IoU, BEV rotated IoU, 3-D IoU) of every frame: one cpd_kitti_overlaps launch per metric;

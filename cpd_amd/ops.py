@@ -827,6 +827,65 @@ def wbf_cluster_cpu(boxes, scores, seg_start, seg_count, seg_thresh, seg_mode):
     return out_boxes, out_scores, out_count, cluster_of
 
 
+K2W_FRAME_WORDS, K2W_TILE, K2W_PREDICT, K2W_CAMERA = 26, 1024, 0, 1      # CPD_K2W_* of include/cpd_hip.h
+
+
+def kitti_fov_points(points, frame_start, max_len, frames, z_shift=1.55, n_feat_out=4, out=None, out_index=None, out_count=None,
+                     workspace=None):
+    """cpd_kitti_fov_points: the FOV crop + sensor-height shift of Kitti2WaymoDataset.__getitem__ for a packed batch, queued on the
+    current stream (no host wait). points [n, ld >= 3] float32, frame_start int32 [B + 1], frames int32 [B, K2W_FRAME_WORDS] (all on
+    the device); max_len: a host int >= the longest frame. -> (out [n, n_feat_out], out_count [B]); frame f's kept rows are
+    out[frame_start[f] : frame_start[f] + out_count[f]]. out_index (int32 [n], optional) receives the kept points' in-frame indices."""
+    _need_cuda(points, "points")
+    assert points.dim() == 2 and points.dtype == torch.float32 and points.is_contiguous() and points.shape[1] >= 3
+    n, ld = int(points.shape[0]), int(points.shape[1])
+    batch = int(frame_start.numel()) - 1
+    dev = points.device
+    assert frame_start.dtype == torch.int32 and frame_start.is_cuda and batch >= 0
+    assert frames.dtype == torch.int32 and frames.is_cuda and frames.numel() == batch * K2W_FRAME_WORDS and frames.is_contiguous()
+    if out is None:
+        out = torch.zeros((n, n_feat_out), dtype=torch.float32, device=dev)
+    if out_count is None:
+        out_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * n_feat_out
+    assert out_count.dtype == torch.int32 and out_count.numel() == batch
+    assert out_index is None or (out_index.dtype == torch.int32 and out_index.numel() == n)
+    need = int(lib().cpd_kitti_fov_workspace_bytes(batch, int(max_len)))
+    if workspace is None:
+        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+    assert workspace.numel() * workspace.element_size() >= need
+    check(lib().cpd_kitti_fov_points(ptr(points), n, ld, ptr(frame_start), batch, int(max_len), ptr(frames), float(z_shift),
+                                     int(n_feat_out), ptr(out), ptr(out_index), ptr(out_count), ptr(workspace),
+                                     workspace.numel() * workspace.element_size(), stream()), "cpd_kitti_fov_points")
+    return out, out_count
+
+
+def kitti_export(boxes, scores, labels, seg_start, frames, mode=K2W_PREDICT, out=None):
+    """cpd_kitti_export: generate_single_sample_dict (mode K2W_PREDICT) or the camera block of DetectionsMerger.merge (K2W_CAMERA)
+    for all frames in one launch, queued on the current stream. boxes [n, 7] float32, scores [n] float32, labels [n] int32, seg_start
+    int32 [B + 1], frames int32 [B, K2W_FRAME_WORDS] on the device. `out`: an int32 device buffer of 21 * n + B words to carve the
+    outputs from (so that one copy brings everything back); a fresh one is made if None.
+    -> dict of views: boxes_lidar [n, 7], score [n], label [n] int32, camera [n, 7] (location, dimensions, rotation_y), alpha [n],
+    bbox [n, 4], count [B] int32, and `buffer`."""
+    _need_cuda(boxes, "boxes")
+    n, batch = int(boxes.shape[0]), int(seg_start.numel()) - 1
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.numel() == 7 * n
+    assert scores is None or (scores.dtype == torch.float32 and scores.numel() == n and scores.is_cuda)
+    assert labels is None or (labels.dtype == torch.int32 and labels.numel() == n and labels.is_cuda)
+    assert seg_start.dtype == torch.int32 and seg_start.is_cuda and batch >= 0
+    assert frames.dtype == torch.int32 and frames.is_cuda and frames.numel() == batch * K2W_FRAME_WORDS and frames.is_contiguous()
+    if out is None:
+        out = torch.zeros((21 * n + batch,), dtype=torch.int32, device=boxes.device)
+    assert out.dtype == torch.int32 and out.numel() == 21 * n + batch and out.is_contiguous()
+    cut = [0, 7 * n, 8 * n, 9 * n, 16 * n, 17 * n, 21 * n, 21 * n + batch]
+    ob, os_, ol, oc, oa, obb, cnt = [out[cut[i]:cut[i + 1]] for i in range(7)]
+    check(lib().cpd_kitti_export(ptr(boxes), ptr(scores), ptr(labels), n, ptr(seg_start), batch, ptr(frames), int(mode), ptr(ob),
+                                 ptr(os_), ptr(ol), ptr(oc), ptr(oa), ptr(obb), ptr(cnt), stream()), "cpd_kitti_export")
+    f32 = torch.float32
+    return {"boxes_lidar": ob.view(f32).view(n, 7), "score": os_.view(f32), "label": ol, "camera": oc.view(f32).view(n, 7),
+            "alpha": oa.view(f32), "bbox": obb.view(f32).view(n, 4), "count": cnt, "buffer": out}
+
+
 def nms(boxes_sorted, thresh, normal=False, sync=True):
     """boxes sorted by descending score. Returns kept row ids (device i64 [num]) (sync=True) or
     (keep [n], num_keep [1]) device tensors."""

@@ -452,6 +452,46 @@ int cpd_wbf_cluster(const float *boxes, const float *scores, int n, const int32_
 int cpd_wbf_cluster_cpu(const float *boxes, const float *scores, int n, const int32_t *seg_start, const int32_t *seg_count,
                         const float *seg_thresh, const int32_t *seg_mode, int n_seg, float *out_boxes, float *out_scores,
                         int32_t *out_count, int32_t *cluster_of);
+/* KITTI transfer evaluation of a Waymo-trained detector (Kitti2WaymoDataset, cpd/datasets/kitti/kitti2waymo_dataset.py): the input
+ * stage of __getitem__ (l.414-425) and the output stage of generate_prediction_dicts (l.272-355), each for a whole batch.
+ * Per-frame constants travel as `frames` [batch][CPD_K2W_FRAME_WORDS] 32-bit words on the DEVICE: M = np.dot(V2C.T, R0.T) [4][3] f32
+ * (words 0-11, row major; formed on the host the way Calibration.lidar_to_rect forms it), P2 [3][4] f32 (words 12-23), then the
+ * image height and width as int32 (words 24, 25). All float32 arithmetic is unfused, products and sums from left to right.
+ *
+ * cpd_kitti_fov_points: Calibration.lidar_to_rect + rect_to_img + get_fov_flag (calibration_kitti.py:110-141,
+ * kitti2waymo_dataset.py:102-118) and `points + [0, 0, 1.55, 0]`, `points[:, 3:] = 0`. points [n][ld >= 3] f32, frame f = rows
+ * frame_start[f] .. frame_start[f + 1] (DEVICE int32 [batch + 1]); max_len >= the longest frame sizes the grid.
+ *   rect = [x y z 1] M;  hom = [rect 1] P2^T;  u = hom0 / rect_z, v = hom1 / rect_z (the rectified z, not hom2);  depth = hom2 - P2[2][3]
+ *   keep iff 0 <= u < w, 0 <= v < h, depth >= 0 (NaN and inf compare false)
+ * The kept points of frame f go, in their input order, to rows frame_start[f] .. + out_count[f] of out [n][n_feat_out >= 3] as
+ * [x, y, (float)((double)z + z_shift), 0, ...]; rows beyond are left alone. out_index (optional, int32 [n]) receives each kept
+ * point's index within its frame at the same rows. out_count [batch] i32 stays on the device; -1 for a frame whose bounds are out of
+ * range or longer than max_len (nothing else is written for it). Two launches (per-tile counts, then scatter; a tile is
+ * CPD_K2W_TILE points), no atomics: the result is bitwise repeatable. Workspace: cpd_kitti_fov_workspace_bytes(batch, max_len). */
+#define CPD_K2W_FRAME_WORDS 26
+#define CPD_K2W_BLOCK 256
+#define CPD_K2W_TILE 1024
+size_t cpd_kitti_fov_workspace_bytes(int batch, int max_len);
+int cpd_kitti_fov_points(const float *points, int n, int ld, const int32_t *frame_start, int batch, int max_len, const void *frames,
+                         double z_shift, int n_feat_out, float *out, int32_t *out_index, int32_t *out_count, void *workspace,
+                         size_t workspace_bytes, cpd_stream_t stream);
+/* cpd_kitti_export: the final detections of a batch to KITTI annotations. boxes [n][7] f32, scores [n] f32, labels [n] i32 (1-based),
+ * frame f = rows seg_start[f] .. seg_start[f + 1] (DEVICE int32 [batch + 1]); one workgroup per frame. The inputs are not written.
+ * CPD_K2W_PREDICT restates generate_single_sample_dict op by op in its dtypes (numpy >= 2 scalar rules): z -= 1.55; where the frame
+ * holds a label != 0, boxes of label != 0 get z += 0.1, l -= 0.2, w -= 0.2, h -= 0.1 and the frame keeps l < 5 (stable); label 1
+ * moves its centre to whichever of +-new_d / 2 along the heading is nearer the origin (float64; new_d = 0.1 + min(|c|, 60) / 60 * 0.3
+ * in float32; a tie takes the negative candidate), rounded to float32 when stored; then the camera part. CPD_K2W_CAMERA runs the
+ * camera part alone on every box (merge_detections.py:247-255): boxes3d_lidar_to_kitti_camera with its in-place z -= h / 2
+ * (box_utils.py:152-166), boxes3d_to_corners3d_kitti_camera, rect_to_img of the 8 corners, min / max, clip to [0, w - 1] /
+ * [0, h - 1] (box_utils.py:169-235), alpha = -atan2(-y, x) + ry.
+ * Outputs, frame f's kept boxes in rows seg_start[f] .. + out_count[f], rows beyond left alone: out_boxes [n][7] (boxes_lidar, z at
+ * the bottom centre), out_scores [n], out_labels [n], out_camera [n][7] = location, dimensions (l, h, w), rotation_y, out_alpha [n],
+ * out_bbox [n][4]; out_count [batch] i32, -1 for a frame whose bounds are out of range. scores / labels may be NULL in camera mode. */
+#define CPD_K2W_PREDICT 0
+#define CPD_K2W_CAMERA 1
+int cpd_kitti_export(const float *boxes, const float *scores, const int32_t *labels, int n, const int32_t *seg_start, int batch,
+                     const void *frames, int mode, float *out_boxes, float *out_scores, int32_t *out_labels, float *out_camera,
+                     float *out_alpha, float *out_bbox, int32_t *out_count, cpd_stream_t stream);
 /* boxes_iou_bev_cpu (iou3d_cpu.cpp:232-252): HOST pointers, runs on the calling thread. This is
  * the one CPU entry point the reference extension itself exports (used by the dataloader's
  * gt-sampling, database_sampler.py:445-446); it is product code, not the test oracle.        */
