@@ -79,6 +79,12 @@ SIGNATURES = {
     "cpd_center_decode_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "cpd_center_decode": (_I, [_VP, _VP, _VP, _VP, _VP, _I, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _F, _FP, _FP, _FP, _F,
                                _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_center_peaks_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "cpd_center_peaks": (_I, [_VP, _I, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_peak_rulebook": (_I, [_VP, _I, _I, _I, _I, _VP, _VP]),
+    "cpd_center_decode_at_peaks_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "cpd_center_decode_at_peaks": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I3, _I, _I, _I, _I, _I, _F, _FP, _FP, _FP, _F,
+                                        _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_boxes_overlap_bev": (_I, [_VP, _I, _VP, _I, _VP, _VP]),
     "cpd_boxes_iou_bev": (_I, [_VP, _I, _VP, _I, _VP, _VP]),
     "cpd_boxes_iou3d": (_I, [_VP, _I, _VP, _I, _VP, _VP]),

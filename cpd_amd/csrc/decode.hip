@@ -12,6 +12,13 @@
 //                       (block_topk); either way a 1024-wide bitonic sort in LDS
 //   decode_kernel     : one workgroup: second top-K, gather, decode, mask, block-scan compaction
 // Ties are broken by ascending flat index (torch.topk leaves tie order unspecified).
+//
+// The same pipeline cut at the peaks (cpd_center_peaks -> cpd_peak_rulebook -> cpd_center_decode_at_peaks), for a head that evaluates
+// its regression branches at the K winners only: the selection (topk_class_kernel + the rank merge) needs the hm map alone; the
+// winners' pixels then name the 9 hidden sites each that the branches' last 3 x 3 convolution reads, the caller computes those hidden
+// rows (one gather_conv launch over the table of cpd_peak_rulebook), and the finish forms the regression values of every peak in
+// fp32 and runs decode_box, the masks and the compaction of decode_kernel -- the same functions, so the two paths differ by the
+// summation order of the last convolution and nothing else.
 #include "common.h"
 
 namespace {
@@ -214,14 +221,76 @@ __global__ void __launch_bounds__(1024) topk_class_kernel(MapView hm_all, long l
     }
 }
 
-struct DecodeParams {
-    MapView center, center_z, dim, rot;
-    long long sample_stride;
-    int num_class, h, w, K;
+struct DecodeGeom {
+    int w;
     float stride, vx, vy, lox, loy;
     float lim[6];
     float score_thresh;
 };
+
+struct DecodeParams {
+    MapView center, center_z, dim, rot;
+    long long sample_stride;
+    int num_class, h, w, K;
+    DecodeGeom g;
+};
+
+// the K best of the num_class x K per-class candidates, in (score descending, candidate index ascending) order. The per-class lists
+// arrive SORTED (topk_class_kernel), so a candidate's place in the merged order is a sum of ranks: its own position, the entries of
+// the classes before it that are >= its key, those of the classes after it that are > its key -- two binary searches per candidate
+// instead of a radix select + bitonic sort over all of them (round 5: 54 -> 13 us at 3 x 500; the same order, bit for bit).
+// On return sm.packed[0..K) = (key << 32 | ~candidate index) of the winners in their final order.
+__device__ __forceinline__ void merge_class_lists(const float *__restrict__ s1, int num_class, int K, TopkSmem &sm) {
+    const int n = num_class * K;
+    for (int i2 = threadIdx.x; i2 < n; i2 += blockDim.x) {
+        const int c = i2 / K, j = i2 - c * K;
+        const uint32_t key = float_key(s1[i2]);
+        int rank = j;
+        for (int c2 = 0; c2 < num_class; ++c2) {
+            if (c2 == c) continue;
+            const float *l = s1 + (size_t)c2 * K;
+            int lo = 0, hi = K;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                const uint32_t km = float_key(l[mid]);
+                if (c2 < c ? km >= key : km > key) lo = mid + 1; else hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < K) sm.packed[rank] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)i2);
+    }
+    __syncthreads();
+}
+
+// one winner's box from its pixel and its eight regression values r = (center x, center y, center_z, dim 0..2, rot cos, rot sin;
+// center_head.py:266-267) -> does it pass the POST_CENTER_LIMIT_RANGE and SCORE_THRESH masks
+__device__ __forceinline__ bool decode_box(const DecodeGeom &g, int ind, float sc, const float r[8], float bx[7]) {
+    const float xs = (float)(ind % g.w), ys = (float)(ind / g.w);
+    bx[0] = (xs + r[0]) * g.stride * g.vx + g.lox;
+    bx[1] = (ys + r[1]) * g.stride * g.vy + g.loy;
+    bx[2] = r[2];
+    bx[3] = expf(r[3]);
+    bx[4] = expf(r[4]);
+    bx[5] = expf(r[5]);
+    bx[6] = atan2f(r[7], r[6]);
+    bool ok = bx[0] >= g.lim[0] && bx[1] >= g.lim[1] && bx[2] >= g.lim[2] && bx[0] <= g.lim[3] &&
+              bx[1] <= g.lim[4] && bx[2] <= g.lim[5];
+    return ok && (sc > g.score_thresh);
+}
+
+// order-preserving compaction of a frame's kept winners (thread k = winner k) + the frame's count
+__device__ __forceinline__ void compact_boxes(uint32_t keep, const float bx[7], float sc, int cls, TopkSmem &sm, float *__restrict__ boxes,
+                                              float *__restrict__ scores, int32_t *__restrict__ labels, int32_t *__restrict__ n_out) {
+    uint32_t tot;
+    uint32_t pos = block_excl_scan(keep, sm.scan, &tot);
+    if (keep) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) boxes[(size_t)pos * 7 + c] = bx[c];
+        scores[pos] = sc;
+        labels[pos] = cls;
+    }
+    if (threadIdx.x == 0) *n_out = (int32_t)tot;
+}
 
 __global__ void __launch_bounds__(1024) decode_kernel(DecodeParams q, const float *__restrict__ s1,
                                                       const int32_t *__restrict__ i1, float *__restrict__ boxes,
@@ -240,31 +309,7 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecodeParams q, const floa
     q.center_z = q.center_z.sample(bsmp, q.sample_stride);
     q.dim = q.dim.sample(bsmp, q.sample_stride);
     q.rot = q.rot.sample(bsmp, q.sample_stride);
-    // the K best of the num_class x K per-class candidates, in (score descending, candidate index ascending) order. The per-class lists
-    // arrive SORTED (topk_class_kernel), so a candidate's place in the merged order is a sum of ranks: its own position, the entries of
-    // the classes before it that are >= its key, those of the classes after it that are > its key -- two binary searches per candidate
-    // instead of a radix select + bitonic sort over all of them (round 5: 54 -> 13 us at 3 x 500; the same order, bit for bit).
-    {
-        const int n = q.num_class * K;
-        for (int i2 = threadIdx.x; i2 < n; i2 += blockDim.x) {
-            const int c = i2 / K, j = i2 - c * K;
-            const uint32_t key = float_key(s1[i2]);
-            int rank = j;
-            for (int c2 = 0; c2 < q.num_class; ++c2) {
-                if (c2 == c) continue;
-                const float *l = s1 + (size_t)c2 * K;
-                int lo = 0, hi = K;
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    const uint32_t km = float_key(l[mid]);
-                    if (c2 < c ? km >= key : km > key) lo = mid + 1; else hi = mid;
-                }
-                rank += lo;
-            }
-            if (rank < K) sm.packed[rank] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)i2);
-        }
-        __syncthreads();
-    }
+    merge_class_lists(s1, q.num_class, K, sm);
     const int k = threadIdx.x;
     float bx[7];
     float sc = 0.f;
@@ -276,29 +321,168 @@ __global__ void __launch_bounds__(1024) decode_kernel(DecodeParams q, const floa
         const int i2 = (int)(~(uint32_t)p);
         cls = i2 / K;
         const int ind = i1[i2];
-        const float xs = (float)(ind % q.w), ys = (float)(ind / q.w);
-        bx[0] = (xs + q.center.at(ind, 0)) * q.stride * q.vx + q.lox;
-        bx[1] = (ys + q.center.at(ind, 1)) * q.stride * q.vy + q.loy;
-        bx[2] = q.center_z.at(ind, 0);
-        bx[3] = expf(q.dim.at(ind, 0));
-        bx[4] = expf(q.dim.at(ind, 1));
-        bx[5] = expf(q.dim.at(ind, 2));
-        bx[6] = atan2f(q.rot.at(ind, 1), q.rot.at(ind, 0));  // rot[0]=cos, rot[1]=sin (center_head.py:266-267)
-        bool ok = bx[0] >= q.lim[0] && bx[1] >= q.lim[1] && bx[2] >= q.lim[2] && bx[0] <= q.lim[3] &&
-                  bx[1] <= q.lim[4] && bx[2] <= q.lim[5];
-        ok = ok && (sc > q.score_thresh);
-        keep = ok ? 1u : 0u;
+        const float r[8] = {q.center.at(ind, 0), q.center.at(ind, 1), q.center_z.at(ind, 0), q.dim.at(ind, 0),
+                            q.dim.at(ind, 1),    q.dim.at(ind, 2),    q.rot.at(ind, 0),      q.rot.at(ind, 1)};
+        keep = decode_box(q.g, ind, sc, r, bx) ? 1u : 0u;
     }
     __syncthreads();
-    uint32_t tot;
-    uint32_t pos = block_excl_scan(keep, sm.scan, &tot);
-    if (keep) {
-#pragma unroll
-        for (int c = 0; c < 7; ++c) boxes[(size_t)pos * 7 + c] = bx[c];
-        scores[pos] = sc;
-        labels[pos] = cls;
+    compact_boxes(keep, bx, sc, cls, sm, boxes, scores, labels, n_out);
+}
+
+// ---- the pipeline cut at the peaks ----
+// the selection alone: one workgroup per frame merges the per-class lists and writes the K winners in their final order
+__global__ void __launch_bounds__(1024) peaks_kernel(int num_class, int K, const float *__restrict__ s1, const int32_t *__restrict__ i1,
+                                                     float *__restrict__ peak_score, int32_t *__restrict__ peak_cand,
+                                                     int32_t *__restrict__ peak_ind) {
+    __shared__ TopkSmem sm;
+    const int bsmp = blockIdx.x;
+    s1 += (size_t)bsmp * num_class * K;
+    i1 += (size_t)bsmp * num_class * K;
+    merge_class_lists(s1, num_class, K, sm);
+    const int k = threadIdx.x;
+    if (k < K) {
+        const unsigned long long p = sm.packed[k];
+        const int i2 = (int)(~(uint32_t)p);
+        peak_score[(size_t)bsmp * K + k] = float_unkey((uint32_t)(p >> 32));
+        peak_cand[(size_t)bsmp * K + k] = i2;
+        peak_ind[(size_t)bsmp * K + k] = i1[i2];
     }
-    if (threadIdx.x == 0) *n_out = (int32_t)tot;
+}
+
+// row (peak * 9 + t) of the table = the hidden site at the peak's pixel + tap t's offset; column u = the shared map's row at that
+// site + tap u's offset, -1 outside the image; a hidden site outside the image (or a pixel index that is no pixel) has no input at all
+__global__ void __launch_bounds__(256) peak_rulebook_kernel(const int32_t *__restrict__ peak_ind, int n_peaks, int K, int h, int w,
+                                                            int32_t *__restrict__ nbr) {
+    const long long n_out = (long long)n_peaks * 9;
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_out) return;
+    const int p = (int)(j / 9), t = (int)(j - (long long)p * 9);
+    const int b = p / K;
+    const int ind = peak_ind[p];
+    const int sy = ind / w + t / 3 - 1, sx = ind % w + t % 3 - 1;
+    const bool site = ind >= 0 && ind < h * w && (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w;
+    int u = 0;
+    for (int ky = 0; ky < 3; ++ky)
+        for (int kx = 0; kx < 3; ++kx, ++u) {
+            const int iy = sy - 1 + ky, ix = sx - 1 + kx;
+            int32_t r = -1;
+            if (site && (unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) r = (int32_t)(((long long)b * h + iy) * w + ix);
+            nbr[(size_t)u * n_out + j] = r;
+        }
+}
+
+// the branches' last 3 x 3 convolution at the peaks: reg[o] = bias[o] + sum over the taps whose hidden site is INSIDE the image (the
+// convolution pads the hidden map with zeros: a site outside contributes nothing, whatever its row holds) of
+// hidden[peak * 9 + t] . W[t][:, o]. A wave owns PP peaks and lane l the hidden channels 4l .. 4l + 3 of every 256-channel slab; the
+// workgroup stages one (tap, slab) of the weight image in LDS at a time and every wave applies it to all its peaks (a wave per peak
+// reading its weights from global memory moved the 73 KB image once per peak: 1.7 GB per 48 frames, 780 us). Fixed summation order:
+// a lane-local fmaf chain over taps and channels, then a butterfly over the lanes.
+template <int NR, int PP>
+__global__ void __launch_bounds__(256) peak_regress_kernel(const int32_t *__restrict__ peak_ind, int n_peaks, int h, int w,
+                                                           const float *__restrict__ hidden, int hid_ld, int c_hid,
+                                                           const float *__restrict__ w_last, const float *__restrict__ bias, int n_reg,
+                                                           float *__restrict__ reg) {
+    __shared__ float wl[256 * NR];                 // [channel of the slab][NR]: columns past n_reg and channels past c_hid are zero
+    const int lane = threadIdx.x & 63;
+    const int p0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * PP;
+    int py[PP], px[PP];
+#pragma unroll
+    for (int i = 0; i < PP; ++i) {
+        const int ind = p0 + i < n_peaks ? peak_ind[p0 + i] : -1;
+        const bool pixel = ind >= 0 && ind < h * w;
+        py[i] = pixel ? ind / w : -4;              // (-4: every tap of the peak is outside)
+        px[i] = pixel ? ind % w : -4;
+    }
+    float acc[PP][NR];
+#pragma unroll
+    for (int i = 0; i < PP; ++i)
+#pragma unroll
+        for (int o = 0; o < NR; ++o) acc[i][o] = 0.f;
+    for (int t = 0; t < 9; ++t) {
+        const int dy = t / 3 - 1, dx = t % 3 - 1;
+        for (int cb = 0; cb < c_hid; cb += 256) {
+            __syncthreads();                       // the previous stage's readers are done
+            for (int i = threadIdx.x; i < 256 * NR; i += blockDim.x) {
+                const int c = cb + i / NR, o = i % NR;
+                wl[i] = (c < c_hid && o < n_reg) ? w_last[((size_t)t * c_hid + c) * n_reg + o] : 0.f;
+            }
+            __syncthreads();
+            const int c0 = cb + lane * 4;
+            if (c0 < c_hid) {
+                float wr[4][NR];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int o = 0; o < NR; ++o) wr[j][o] = wl[(lane * 4 + j) * NR + o];
+#pragma unroll
+                for (int i = 0; i < PP; ++i) {
+                    if (!((unsigned)(py[i] + dy) < (unsigned)h && (unsigned)(px[i] + dx) < (unsigned)w)) continue;      // (wave-uniform)
+                    const float4 hv = *reinterpret_cast<const float4 *>(hidden + ((size_t)(p0 + i) * 9 + t) * hid_ld + c0);
+                    const float hx[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int o = 0; o < NR; ++o) acc[i][o] = fmaf(hx[j], wr[j][o], acc[i][o]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < PP; ++i)
+#pragma unroll
+        for (int o = 0; o < NR; ++o) {
+            float v = acc[i][o];
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+            if (lane == 0 && p0 + i < n_peaks && o < n_reg) reg[(size_t)(p0 + i) * n_reg + o] = v + bias[o];
+        }
+}
+
+struct PeakDecodeParams {
+    int K, n_reg;
+    int off[4];         // first channel of center, center_z, dim, rot among the n_reg regression values
+    DecodeGeom g;
+};
+
+__global__ void __launch_bounds__(1024) decode_peaks_kernel(PeakDecodeParams q, const float *__restrict__ peak_score,
+                                                            const int32_t *__restrict__ peak_cand, const int32_t *__restrict__ peak_ind,
+                                                            const float *__restrict__ reg, float *__restrict__ boxes,
+                                                            float *__restrict__ scores, int32_t *__restrict__ labels,
+                                                            int32_t *__restrict__ n_out) {
+    __shared__ TopkSmem sm;
+    const int K = q.K;
+    const int bsmp = blockIdx.x;
+    const size_t o = (size_t)bsmp * K;
+    const int k = threadIdx.x;
+    float bx[7];
+    float sc = 0.f;
+    int cls = 0;
+    uint32_t keep = 0;
+    if (k < K) {
+        sc = peak_score[o + k];
+        cls = peak_cand[o + k] / K;
+        const float *v = reg + (o + k) * q.n_reg;
+        const float r[8] = {v[q.off[0]], v[q.off[0] + 1], v[q.off[1]], v[q.off[2]], v[q.off[2] + 1], v[q.off[2] + 2], v[q.off[3]], v[q.off[3] + 1]};
+        keep = decode_box(q.g, peak_ind[o + k], sc, r, bx) ? 1u : 0u;
+    }
+    compact_boxes(keep, bx, sc, cls, sm, boxes + o * 7, scores + o, labels + o, n_out + bsmp);
+}
+
+static void fill_geom(DecodeGeom &g, int w, float feature_map_stride, const float voxel_xy[2], const float range_lo_xy[2],
+                      const float limit_range[6], float score_thresh) {
+    g.w = w;
+    g.stride = feature_map_stride; g.vx = voxel_xy[0]; g.vy = voxel_xy[1];
+    g.lox = range_lo_xy[0]; g.loy = range_lo_xy[1];
+    for (int i = 0; i < 6; ++i) g.lim[i] = limit_range[i];
+    g.score_thresh = score_thresh;
+}
+
+// what cpd_center_decode refuses, the entry points cut from it refuse with the same codes
+static int check_topk_shape(int batch, int num_class, int h, int w, int k) {
+    if (batch <= 0 || num_class <= 0 || h <= 0 || w <= 0 || k <= 0) return CPD_ERR_ARG;
+    const long long hw = (long long)h * w;
+    if (k > 1024 || k > hw || (long long)num_class * k > (1 << 24) || hw >= (1ll << 31)) return CPD_ERR_UNSUPPORTED;
+    return CPD_OK;
 }
 
 }  // namespace
@@ -316,10 +500,10 @@ extern "C" int cpd_center_decode(const float *hm, const float *center, const flo
                                  int32_t *labels, int32_t *n_out, void *workspace, size_t workspace_bytes,
                                  cpd_stream_t stream) {
     if (!hm || !center || !center_z || !dim || !rot || !boxes || !scores || !labels || !n_out || !workspace ||
-        !voxel_xy || !range_lo_xy || !limit_range || batch <= 0 || num_class <= 0 || h <= 0 || w <= 0 || k <= 0)
+        !voxel_xy || !range_lo_xy || !limit_range)
         return CPD_ERR_ARG;
+    if (const int rc = check_topk_shape(batch, num_class, h, w, k)) return rc;
     const long long hw = (long long)h * w;
-    if (k > 1024 || k > hw || (long long)num_class * k > (1 << 24) || hw >= (1ll << 31)) return CPD_ERR_UNSUPPORTED;
     if (workspace_bytes < cpd_center_decode_workspace_bytes(batch, num_class, (int)hw, k)) return CPD_ERR_WORKSPACE;
     hipStream_t s = cpd_s(stream);
     float *s1 = (float *)workspace;
@@ -333,10 +517,75 @@ extern "C" int cpd_center_decode(const float *hm, const float *center, const flo
     q.rot = MapView{rot, pix_stride, ch_stride};
     q.sample_stride = sample_stride;
     q.num_class = num_class; q.h = h; q.w = w; q.K = k;
-    q.stride = feature_map_stride; q.vx = voxel_xy[0]; q.vy = voxel_xy[1];
-    q.lox = range_lo_xy[0]; q.loy = range_lo_xy[1];
-    for (int i = 0; i < 6; ++i) q.lim[i] = limit_range[i];
-    q.score_thresh = score_thresh;
+    fill_geom(q.g, w, feature_map_stride, voxel_xy, range_lo_xy, limit_range, score_thresh);
     decode_kernel<<<batch, 1024, 0, s>>>(q, s1, i1, boxes, scores, labels, n_out);
+    return cpd_check_launch();
+}
+
+extern "C" size_t cpd_center_peaks_workspace_bytes(int batch, int num_class, int hw, int k) {
+    return cpd_center_decode_workspace_bytes(batch, num_class, hw, k);
+}
+
+extern "C" int cpd_center_peaks(const float *hm, int batch, long long sample_stride, int pix_stride, int ch_stride, int num_class, int h,
+                                int w, int k, float *peak_score, int32_t *peak_cand, int32_t *peak_ind, void *workspace,
+                                size_t workspace_bytes, cpd_stream_t stream) {
+    if (!hm || !peak_score || !peak_cand || !peak_ind || !workspace) return CPD_ERR_ARG;
+    if (const int rc = check_topk_shape(batch, num_class, h, w, k)) return rc;
+    const int hw = h * w;
+    if (workspace_bytes < cpd_center_peaks_workspace_bytes(batch, num_class, hw, k)) return CPD_ERR_WORKSPACE;
+    hipStream_t s = cpd_s(stream);
+    float *s1 = (float *)workspace;
+    int32_t *i1 = (int32_t *)((char *)workspace + cpd_align((size_t)batch * num_class * k * 4));
+    topk_class_kernel<<<dim3(num_class, batch), 1024, 0, s>>>(MapView{hm, pix_stride, ch_stride}, sample_stride, num_class, hw, k, s1, i1);
+    peaks_kernel<<<batch, 1024, 0, s>>>(num_class, k, s1, i1, peak_score, peak_cand, peak_ind);
+    return cpd_check_launch();
+}
+
+extern "C" int cpd_peak_rulebook(const int32_t *peak_ind, int batch, int k, int h, int w, int32_t *nbr, cpd_stream_t stream) {
+    if (!peak_ind || !nbr || batch <= 0 || k <= 0 || h <= 0 || w <= 0) return CPD_ERR_ARG;
+    const long long hw = (long long)h * w;
+    if (k > 1024 || k > hw || batch * hw >= (1ll << 31) || (long long)batch * k * 9 >= (1ll << 31)) return CPD_ERR_UNSUPPORTED;
+    const long long n_out = (long long)batch * k * 9;
+    peak_rulebook_kernel<<<cpd_div_up(n_out, 256), 256, 0, cpd_s(stream)>>>(peak_ind, batch * k, k, h, w, nbr);
+    return cpd_check_launch();
+}
+
+extern "C" size_t cpd_center_decode_at_peaks_workspace_bytes(int batch, int k, int n_reg) {
+    if (batch <= 0 || k <= 0 || n_reg <= 0) return 0;
+    return cpd_align((size_t)batch * k * n_reg * 4);
+}
+
+extern "C" int cpd_center_decode_at_peaks(const float *peak_score, const int32_t *peak_cand, const int32_t *peak_ind, const float *hidden,
+                                          int hidden_ld, int c_hid, const float *w_last, const float *bias, int n_reg,
+                                          const int32_t reg_offsets[4], int batch, int num_class, int h, int w, int k,
+                                          float feature_map_stride, const float voxel_xy[2], const float range_lo_xy[2],
+                                          const float limit_range[6], float score_thresh, float *boxes, float *scores, int32_t *labels,
+                                          int32_t *n_out, void *workspace, size_t workspace_bytes, cpd_stream_t stream) {
+    if (!peak_score || !peak_cand || !peak_ind || !hidden || !w_last || !bias || !reg_offsets || !boxes || !scores || !labels || !n_out ||
+        !workspace || !voxel_xy || !range_lo_xy || !limit_range || c_hid <= 0 || n_reg <= 0 || hidden_ld < c_hid)
+        return CPD_ERR_ARG;
+    if (const int rc = check_topk_shape(batch, num_class, h, w, k)) return rc;
+    static const int width[4] = {2, 1, 3, 2};        // center, center_z, dim, rot
+    for (int i = 0; i < 4; ++i)
+        if (reg_offsets[i] < 0 || reg_offsets[i] + width[i] > n_reg) return CPD_ERR_ARG;
+    // (16-byte row pieces; at most 16 regression values: the shipped heads have 8)
+    if (n_reg > 16 || c_hid % 4 || hidden_ld % 4 || (((uintptr_t)hidden) & 15)) return CPD_ERR_UNSUPPORTED;
+    if (workspace_bytes < cpd_center_decode_at_peaks_workspace_bytes(batch, k, n_reg)) return CPD_ERR_WORKSPACE;
+    hipStream_t s = cpd_s(stream);
+    float *reg = (float *)workspace;
+    const int n_peaks = batch * k;
+    // peaks per wave: 8 once that still gives every CU two workgroups, else 2 (small batches: more, shorter workgroups)
+    const bool wide = n_peaks >= 16384;
+    const int blocks = cpd_div_up(n_peaks, 4 * (wide ? 8 : 2));
+#define CPD_PEAK_REGRESS(NR, PP) \
+    peak_regress_kernel<NR, PP><<<blocks, 256, 0, s>>>(peak_ind, n_peaks, h, w, hidden, hidden_ld, c_hid, w_last, bias, n_reg, reg)
+    if (n_reg <= 8) { if (wide) CPD_PEAK_REGRESS(8, 8); else CPD_PEAK_REGRESS(8, 2); }
+    else { if (wide) CPD_PEAK_REGRESS(16, 8); else CPD_PEAK_REGRESS(16, 2); }
+#undef CPD_PEAK_REGRESS
+    PeakDecodeParams q;
+    q.K = k; q.n_reg = n_reg;
+    for (int i = 0; i < 4; ++i) q.off[i] = reg_offsets[i];
+    fill_geom(q.g, w, feature_map_stride, voxel_xy, range_lo_xy, limit_range, score_thresh);
+    decode_peaks_kernel<<<batch, 1024, 0, s>>>(q, peak_score, peak_cand, peak_ind, reg, boxes, scores, labels, n_out);
     return cpd_check_launch();
 }

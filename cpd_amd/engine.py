@@ -10,6 +10,7 @@ Weights come in under the reference's own state_dict names (so a CPD checkpoint 
 """
 import contextlib
 import math
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, NamedTuple, Optional
 
@@ -100,6 +101,20 @@ class ModelConfig:
     deblock_side_stream: bool = True
     deblock_side_stream_max_frames: int = 8
     index_side_stream_max_frames: int = 1 << 30
+    # CenterHead's regression branches (center, center_z, dim, rot) only at the max_obj_per_sample merged top-K pixels of each frame -- the
+    # only places the decode reads them (1.4 % of a 188 x 188 map): the hm branch alone runs over every pixel, the selection
+    # (ops.center_peaks) names the winners, the regression branches' first convs run as ONE gather_conv over the 9 hidden sites around
+    # each winner (ops.peak_rulebook) and ops.center_decode_at_peaks applies their last convs in fp32 and decodes. Scores, labels and
+    # peak pixels are bit for bit those of the full maps (the hm branch takes the same kernel and tile as inside the fused layers: a batch
+    # shape where it would not keeps the full maps, engine._head_at_peaks_ok); boxes differ by the last conv's fp32 summation order.
+    # (Bit for bit on the unguarded kernels. In a range-guarded step head2_hm pre-scales its input by the power of two of the hm branch's
+    # 64 hidden channels, the fused head2 by that of all 320: where the exponents differ the fp16 low terms round differently and a score
+    # can differ in its last bits -- fp32-level, like everything else a guarded step changes.)
+    # Callers that want the head maps (return_intermediates, bev_and_head on its own) get the full maps. CPD_HEAD_AT_PEAKS=0 in the
+    # environment turns it off at construction (same-box A/B). Batches below head_at_peaks_min_frames keep the full maps
+    # (the measured pairs).
+    head_at_peaks: bool = True
+    head_at_peaks_min_frames: int = 4
 
     @property
     def grid_zyx(self):
@@ -264,6 +279,15 @@ class _StageTables(NamedTuple):
     canon: Optional[tuple]     # (held: the chunk-wise tables were built from it)
 
 
+class _PeakHead(NamedTuple):
+    """a CenterHead cut at the peaks, as decode_and_nms takes it: the winners of every frame in their final order (ops.center_peaks)
+    and the regression branches' hidden rows at the 9 sites around each (row order of ops.peak_rulebook)"""
+    score: torch.Tensor
+    cand: torch.Tensor
+    ind: torch.Tensor
+    hidden: torch.Tensor
+
+
 class CenterPointEngine:
     """points [N, C] (device f32)  ->  {'pred_boxes','pred_scores','pred_labels'} per frame."""
 
@@ -282,6 +306,9 @@ class CenterPointEngine:
         self._voxelizers = [self.voxelizer]
         self._group_voxelizers = []
         self._bev_cache = {}
+        self.last_head_at_peaks = False    # did the last step evaluate the regression branches at the peaks only (diagnostics, tests)
+        self._peaks = None                 # (a CenterHead's layers cut at the peaks, _build_head; other dense heads leave it None)
+        self.head_at_peaks = bool(cfg.head_at_peaks) and os.environ.get("CPD_HEAD_AT_PEAKS", "1") != "0"
         self._build_layers()
 
     # ------------------------------------------------------------------ weights
@@ -316,6 +343,18 @@ class CenterPointEngine:
         self.head1 = _Layer(w1, s1, t1, True, self.device)
         self.head2 = _Layer(w2, None, b2, False, self.device)
         self.head_ld = 16 * ((w2.shape[2] + 15) // 16)
+        # ... and cut at the peaks (ModelConfig.head_at_peaks): the hm branch on its own, the regression branches' first convs side by
+        # side, their last convs as the fp32 image of the native finish
+        names = self.cfg.head_names()
+        P = layer_table.split_branches_at(*zip(*first), lw, lb, names.index("hm"))
+        hm_ld = 16 * ((self.cfg.num_class + 15) // 16)
+        w_last, b_last = P["rest2"]
+        off = dict(zip([n for n in names if n != "hm"], (c0 for c0, _ in P["rest_slices"])))
+        self._peaks = dict(head1_hm=_Layer(*P["keep1"], True, self.device), head2_hm=_Layer(P["keep2"][0], None, P["keep2"][1], False, self.device),
+                           reg1=_Layer(*P["rest1"], True, self.device), hm_ld=hm_ld,
+                           w_last=w_last.to(device=self.device, dtype=torch.float32).contiguous(),
+                           b_last=b_last.to(device=self.device, dtype=torch.float32).contiguous(),
+                           offsets=[off["center"], off["center_z"], off["dim"], off["rot"]])
 
     def _final_shape(self):
         return final_shape(self.cfg)
@@ -337,7 +376,7 @@ class CenterPointEngine:
         if self.cfg.conv_math == "f16x2" and self.cfg.range_guard:
             if getattr(self, "_rb_pool", None) is None:
                 # one block per conv launch of a step: 20 sparse layers + conv_out, the BEV levels' convs, the concat buffer,
-                # shared conv + the two head launches (+ slack for callers that run the stages on their own)
+                # shared conv + the two head launches (three with the head cut at the peaks; + slack for callers that run the stages on their own)
                 n = 21 + sum(k + 1 for k in self.cfg.bev_layer_nums) + 1 + 3 + 16
                 self._rb_pool = ops.absmax_blocks(n, self.device)
             else:
@@ -513,10 +552,32 @@ class CenterPointEngine:
                 ops.conv3x3_rows_tile(batch, h, w, self.head1.c_in, self.head1.c_out) in ((256, 64), (128, 64)) and
                 ops.conv3x3_rows_tile(batch, h, w, self.head2.c_in, self.head2.c_out) in ((256, 16), (128, 16)))
 
-    def bev_and_head(self, dense_rows, batch, h, w, pairs=False):
+    def _head_at_peaks_ok(self, batch, h, w):
+        """does this batch shape take the head cut at the peaks (ModelConfig.head_at_peaks)? Only where the hm branch's two layers get
+        the window kernel and the very tile they have inside the fused layers (64 -> 64 on head1's 64-column tile, 64 -> num_class on
+        head2's 16-column tile, the hm columns a whole tile of head1): the same kernel on the same tile does the same arithmetic, so
+        the scores are those of the full maps bit for bit. Any other shape keeps the full maps."""
+        P, cfg = self._peaks, self.cfg
+        if P is None or not self.head_at_peaks or batch < cfg.head_at_peaks_min_frames:
+            return False
+        key = ("head_at_peaks", batch, h, w)
+        if key not in self._bev_cache:
+            k = cfg.max_obj_per_sample
+            tile = lambda L: ops.conv3x3_rows_tile(batch, h, w, L.c_in, L.c_out, cfg.conv_math) if cfg.conv_math in ("f16x2", "bf16x3") else None
+            t1, t2 = tile(self.head1), tile(self.head2)
+            hm_col = cfg.head_names().index("hm") * P["head1_hm"].c_out          # first hidden column of the hm branch in head1
+            self._bev_cache[key] = bool(
+                t1 is not None and t2 is not None and t1 == tile(P["head1_hm"]) and t2 == tile(P["head2_hm"]) and
+                P["head1_hm"].c_out == t1[1] and hm_col % t1[1] == 0 and k <= 1024 and k <= h * w and
+                batch * k * 9 * 4 * P["reg1"].c_out < 0xfff00000)
+        return self._bev_cache[key]
+
+    def bev_and_head(self, dense_rows, batch, h, w, pairs=False, at_peaks=False):
         """BaseBEVBackbone.forward (base_bev_backbone.py:85-122) + CenterHead convs
         (center_head.py:323-330) on channels-last rows [batch*h*w, C]. `pairs`: `dense_rows` and every map up to the head's hidden
-        layer are fp16-pair maps (ModelConfig.pair_rows_dense); the returned concat map is then a pair map, the head rows are fp32."""
+        layer are fp16-pair maps (ModelConfig.pair_rows_dense); the returned concat map is then a pair map, the head rows are fp32.
+        `at_peaks` (forward() only, where _head_at_peaks_ok): instead of the head rows, what decode_and_nms takes of a head cut at the
+        peaks (_PeakHead)."""
         cfg = self.cfg
         pk = dict(in_pairs=True, out_pairs=True) if pairs else {}
         T = bev_tables(self._bev_cache, batch, h, w, self.device)
@@ -575,6 +636,8 @@ class CenterPointEngine:
         for ev in joins:
             main.wait_event(ev)
         self._rb = cat_rb
+        if at_peaks:
+            return cat, self._head_rows_at_peaks(cat, batch, h, w, T, pairs)
         return cat, self._head_rows(cat, batch, h, w, T, pairs)
 
     def _head_rows(self, cat, batch, h, w, T, pairs):
@@ -587,19 +650,45 @@ class CenterPointEngine:
         self._conv(self.head2, h1, T["s1"][0], n_full, out=out, dense=pairs, in_pairs=pairs)
         return out
 
+    def _head_rows_at_peaks(self, cat, batch, h, w, T, pairs):
+        """the head cut at the peaks: shared conv and the hm branch over every pixel (the window kernels, as in _head_rows), the
+        selection, then the regression branches' first convs over the 9 hidden sites around each winner -- one gather_conv launch over
+        the shared map's rows. Nothing is read back; every shape is fixed by (batch, max_obj_per_sample, h, w)."""
+        P, cfg = self._peaks, self.cfg
+        pk = dict(in_pairs=True, out_pairs=True) if pairs else {}
+        n_full = batch * h * w
+        k = cfg.max_obj_per_sample
+        s = self._conv(self.shared, cat, T["s1"][0], n_full, dense=True, **pk)
+        s_rb = self._rb                                        # the shared map has two readers
+        h1 = self._conv(P["head1_hm"], s, T["s1"][0], n_full, dense=True, **pk)
+        hm = torch.empty((n_full, P["hm_ld"]), dtype=torch.float32, device=self.device)
+        self._conv(P["head2_hm"], h1, T["s1"][0], n_full, out=hm, dense=pairs, in_pairs=pairs)
+        score, cand, ind = ops.center_peaks(hm, P["hm_ld"], 1, cfg.num_class, h, w, k, batch=batch, sample_stride=h * w * P["hm_ld"])
+        nbr = ops.peak_rulebook(ind, h, w)
+        self._rb = s_rb
+        hidden = self._conv(P["reg1"], s, nbr, batch * k * 9, in_pairs=pairs)
+        return _PeakHead(score, cand, ind, hidden)
+
     def decode_and_nms(self, head_rows, batch, h, w, raw=False):
         """generate_predicted_boxes (center_head.py:252-303) + class_agnostic_nms
         (model_nms_utils.py:115-134) for all samples of the batch: five launches, nothing read back
-        until the final per-sample counts."""
+        until the final per-sample counts. `head_rows`: the head rows, or the _PeakHead of a head cut at the peaks."""
         cfg = self.cfg
         ld = self.head_ld
         sl = self.head_slices
         base = head_rows
-        boxes, scores, labels, counts = ops.center_decode(
-            base[:, sl["hm"][0]:], base[:, sl["center"][0]:], base[:, sl["center_z"][0]:], base[:, sl["dim"][0]:],
-            base[:, sl["rot"][0]:], ld, 1, cfg.num_class, h, w, cfg.max_obj_per_sample, float(cfg.feature_map_stride),
-            cfg.voxel_size[:2], cfg.point_cloud_range[:2], cfg.post_center_limit_range, cfg.score_thresh, sync=False,
-            batch=batch, sample_stride=h * w * ld)
+        if isinstance(head_rows, _PeakHead):
+            P = self._peaks
+            boxes, scores, labels, counts = ops.center_decode_at_peaks(
+                head_rows.score, head_rows.cand, head_rows.ind, head_rows.hidden, P["reg1"].c_out, P["w_last"], P["b_last"], P["offsets"],
+                cfg.num_class, h, w, float(cfg.feature_map_stride), cfg.voxel_size[:2], cfg.point_cloud_range[:2],
+                cfg.post_center_limit_range, cfg.score_thresh)
+        else:
+            boxes, scores, labels, counts = ops.center_decode(
+                base[:, sl["hm"][0]:], base[:, sl["center"][0]:], base[:, sl["center_z"][0]:], base[:, sl["dim"][0]:],
+                base[:, sl["rot"][0]:], ld, 1, cfg.num_class, h, w, cfg.max_obj_per_sample, float(cfg.feature_map_stride),
+                cfg.voxel_size[:2], cfg.point_cloud_range[:2], cfg.post_center_limit_range, cfg.score_thresh, sync=False,
+                batch=batch, sample_stride=h * w * ld)
         # scores come out sorted descending (top-K order survives the masks), so the
         # topk(NMS_PRE_MAXSIZE) + sort inside nms_gpu are identities (K = 500 <= 4096)
         assert cfg.max_obj_per_sample <= cfg.nms_pre_maxsize
@@ -722,7 +811,9 @@ class CenterPointEngine:
             else:
                 dense = ops.densify_nhwc(x, out_idx, batch, out_shape).view(batch * h * w, d * x.shape[1])
             self._dense_map = dmap
-            cat, head = self.bev_and_head(dense, batch, h, w, pairs=dp)
+            # (callers that get the head rows back keep the full maps)
+            peaks = self.last_head_at_peaks = (not return_intermediates) and self._head_at_peaks_ok(batch, h, w)
+            cat, head = self.bev_and_head(dense, batch, h, w, pairs=dp, at_peaks=peaks)
             results = self.decode_and_nms(head, batch, h, w, raw=proposals is not None)
             if results is not None:
                 break

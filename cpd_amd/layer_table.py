@@ -204,3 +204,16 @@ def fuse_branches(first_w, first_scale, first_shift, last_w, last_bias):
         slices.append((col, co))
         row, col = row + ci, col + co
     return torch.cat(list(first_w), dim=2), torch.cat(list(first_scale)), torch.cat(list(first_shift)), w2, b2, slices
+
+
+def split_branches_at(first_w, first_scale, first_shift, last_w, last_bias, keep):
+    """The same parallel branches cut for a head that runs branch `keep` (CenterHead: the heat map) over every pixel and the others
+    only where the decode reads them. -> dict: "keep1" (w, scale, shift) and "keep2" (w, bias) = branch `keep`'s own two convs (the
+    columns it has in fuse_branches' w1 / s1 / t1; its block of w2); "rest1" (w, scale, shift) = the other branches' first convs side by
+    side, in their order; "rest2" (w [kv, sum Cin, sum Cout], bias) = their last convs block-diagonal (zeros included), the fp32 image of
+    cpd_center_decode_at_peaks; "rest_slices"[i] = (first column, columns) of the i-th other branch in it."""
+    rest = [i for i in range(len(first_w)) if i != keep]
+    pick = lambda xs: [xs[i] for i in rest]
+    w1, s1, t1, w2, b2, slices = fuse_branches(pick(first_w), pick(first_scale), pick(first_shift), pick(last_w), pick(last_bias))
+    return dict(keep1=(first_w[keep], first_scale[keep], first_shift[keep]), keep2=(last_w[keep], last_bias[keep]),
+                rest1=(w1, s1, t1), rest2=(w2, b2), rest_slices=slices)

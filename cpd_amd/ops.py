@@ -617,6 +617,52 @@ def center_decode(hm, center, center_z, dim, rot, pix_stride, ch_stride, num_cla
     return boxes[0, :n], scores[0, :n], labels[0, :n], n
 
 
+def center_peaks(hm, pix_stride, ch_stride, num_class, h, w, k, batch=1, sample_stride=0):
+    """The selection half of center_decode on the hm view alone (cpd_center_peaks): per frame the K winners in their final order ->
+    (score [batch, k] f32, cand [batch, k] i32 (class = cand // k), ind [batch, k] i32 (pixel)). No host synchronisation."""
+    dev = hm.device
+    score = torch.empty((batch, k), dtype=torch.float32, device=dev)
+    cand = torch.empty((batch, k), dtype=torch.int32, device=dev)
+    ind = torch.empty((batch, k), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib().cpd_center_peaks_workspace_bytes(batch, num_class, h * w, k), dtype=torch.uint8, device=dev)
+    check(lib().cpd_center_peaks(ctypes.c_void_p(hm.data_ptr()), int(batch), int(sample_stride), pix_stride, ch_stride, num_class, h, w, k,
+                                 ptr(score), ptr(cand), ptr(ind), ptr(ws), ws.numel(), stream()), "cpd_center_peaks")
+    return score, cand, ind
+
+
+def peak_rulebook(ind, h, w):
+    """ind [batch, k] i32 (center_peaks) -> the table [9, batch * k * 9] of a 3 x 3 / pad 1 convolution evaluated at the 9 sites around
+    every peak (cpd_peak_rulebook): row (b * k + j) * 9 + t = the site at peak (b, j)'s pixel + tap t's offset; -1 outside the image."""
+    batch, k = ind.shape
+    nbr = torch.empty((9, batch * k * 9), dtype=torch.int32, device=ind.device)
+    check(lib().cpd_peak_rulebook(ptr(ind), batch, k, h, w, ptr(nbr), stream()), "cpd_peak_rulebook")
+    return nbr
+
+
+def center_decode_at_peaks(score, cand, ind, hidden, c_hid, w_last, bias, reg_offsets, num_class, h, w, feature_map_stride, voxel_xy,
+                           range_lo_xy, limit_range, score_thresh):
+    """The finish of the decode cut at the peaks (cpd_center_decode_at_peaks): `hidden` = fp32 rows [batch * k * 9, >= c_hid] in
+    peak_rulebook's row order, `w_last` [9, c_hid, n_reg] / `bias` [n_reg] = the branches' last convolutions as one block-diagonal fp32
+    image, `reg_offsets` = first channel of (center, center_z, dim, rot). -> center_decode's capacity-sized device outputs
+    (boxes [batch, k, 7], scores, labels, counts), no host synchronisation."""
+    batch, k = ind.shape
+    dev = ind.device
+    assert hidden.dim() == 2 and hidden.stride(1) == 1 and hidden.shape[0] == batch * k * 9 and hidden.dtype == torch.float32
+    assert w_last.is_contiguous() and tuple(w_last.shape[:2]) == (9, c_hid) and bias.numel() == w_last.shape[2]
+    n_reg = int(w_last.shape[2])
+    boxes = torch.empty((batch, k, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((batch, k), dtype=torch.float32, device=dev)
+    labels = torch.empty((batch, k), dtype=torch.int32, device=dev)
+    n_out = torch.zeros((batch,), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib().cpd_center_decode_at_peaks_workspace_bytes(batch, k, n_reg), dtype=torch.uint8, device=dev)
+    check(lib().cpd_center_decode_at_peaks(
+        ptr(score), ptr(cand), ptr(ind), ctypes.c_void_p(hidden.data_ptr()), hidden.stride(0), int(c_hid), ptr(w_last), ptr(bias), n_reg,
+        iarr(reg_offsets), batch, num_class, h, w, k, float(feature_map_stride), farr(voxel_xy), farr(range_lo_xy), farr(limit_range),
+        float(score_thresh), ptr(boxes), ptr(scores), ptr(labels), ptr(n_out), ptr(ws), ws.numel(), stream()),
+        "cpd_center_decode_at_peaks")
+    return boxes, scores, labels, n_out
+
+
 def nms_batch(boxes, counts, thresh, normal=False):
     """boxes [batch, cap, 7] (descending score per sample), counts [batch] i32 on the device.
     Returns (keep [batch, cap] i64, num_keep [batch] i32), no host synchronisation."""

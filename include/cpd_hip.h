@@ -341,6 +341,38 @@ int cpd_center_decode(const float *hm, const float *center, const float *center_
                       const float limit_range[6], float score_thresh, float *boxes, float *scores,
                       int32_t *labels, int32_t *n_out, void *workspace, size_t workspace_bytes,
                       cpd_stream_t stream);
+/* The same decode cut at the peaks, for a head that evaluates its regression branches only where the decode reads them (the K
+ * merged top-K pixels of each frame). Same kernels and arithmetic as cpd_center_decode for the selection, the box decode, the masks
+ * and the compaction; same error codes (k > 1024, k > h*w: CPD_ERR_UNSUPPORTED). Nothing here synchronises with the host.
+ *
+ * cpd_center_peaks: per-class top-K + the merge over classes on the hm map alone. Per frame, the K winners in their final order:
+ * peak_score [batch,K], peak_cand [batch,K] (candidate index; class = peak_cand / K), peak_ind [batch,K] (pixel y*w + x). */
+size_t cpd_center_peaks_workspace_bytes(int batch, int num_class, int hw, int k);
+int cpd_center_peaks(const float *hm, int batch, long long sample_stride, int pix_stride, int ch_stride,
+                     int num_class, int h, int w, int k, float *peak_score, int32_t *peak_cand,
+                     int32_t *peak_ind, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+/* cpd_peak_rulebook: the neighbour table nbr[9][batch*K*9] of the regression branches' FIRST 3 x 3 / pad 1 convolution, evaluated
+ * at the 9 hidden sites the LAST 3 x 3 convolution reads around each peak. Output row (b*K + k)*9 + t is the hidden site at peak
+ * (b, k)'s pixel + tap t's offset (t = ky*3 + kx, offset (ky - 1, kx - 1): the tap order of cpd_rulebook_conv2d); nbr[u][row] is
+ * the row b*h*w + pixel of the input map at that site + tap u's offset, -1 where that pixel is outside the image, and -1 for every
+ * u where the hidden site itself is outside the image. A neighbour never belongs to another frame. */
+int cpd_peak_rulebook(const int32_t *peak_ind, int batch, int k, int h, int w, int32_t *nbr,
+                      cpd_stream_t stream);
+/* cpd_center_decode_at_peaks: hidden [batch*K*9, c_hid] fp32 rows (pitch hidden_ld floats; row order of cpd_peak_rulebook), the last
+ * convolutions' weights as ONE fp32 image w_last [9][c_hid][n_reg] (block-diagonal over the branches, zeros included) with bias
+ * [n_reg]; reg_offsets = first channel of center (2 values), center_z (1), dim (3), rot (2) among the n_reg. Forms every peak's
+ * regression values in fp32 -- a tap whose hidden site lies outside the image contributes NOTHING (the last convolution pads the
+ * hidden map with zeros; what the hidden row of such a site holds is ignored) -- then decodes, masks and compacts as
+ * cpd_center_decode does. Outputs as cpd_center_decode's. n_reg <= 16, c_hid and hidden_ld multiples of 4, hidden 16-byte aligned. */
+size_t cpd_center_decode_at_peaks_workspace_bytes(int batch, int k, int n_reg);
+int cpd_center_decode_at_peaks(const float *peak_score, const int32_t *peak_cand, const int32_t *peak_ind,
+                               const float *hidden, int hidden_ld, int c_hid, const float *w_last,
+                               const float *bias, int n_reg, const int32_t reg_offsets[4], int batch,
+                               int num_class, int h, int w, int k, float feature_map_stride,
+                               const float voxel_xy[2], const float range_lo_xy[2],
+                               const float limit_range[6], float score_thresh, float *boxes, float *scores,
+                               int32_t *labels, int32_t *n_out, void *workspace, size_t workspace_bytes,
+                               cpd_stream_t stream);
 
 /* ===== B3. iou3d_nms =======================================================================
  * Replaces the iou3d_nms_cuda extension (cpd/ops/iou3d_nms/src/iou3d_nms_api.cpp:11-17).
