@@ -561,15 +561,11 @@ __global__ void __launch_bounds__(T) order_rows_kernel(const uint32_t *__restric
 // + rows of the band left of its brick                       (per line: rank(line, xb0) - rank(line, 0))
 // + rows of its brick in earlier lines                       (per line: rank(line, xb1) - rank(line, xb0))
 // + rows of its own line inside the brick before it          (its own rank - rank(line, xb0)).
-__device__ __forceinline__ uint32_t rank_before(const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ base, long long key,
-                                                long long cells, uint32_t n_total) {
-    if (key >= cells) return n_total;
-    const uint64_t w = bitmap[key >> 6];
-    return base[key >> 6] + (uint32_t)__popcll(w & ((1ull << (key & 63)) - 1ull));
-}
-
+// (Rank queries at cells that need not be occupied: index_rank_before, which also serves an index whose prefix covers only the scan
+// blocks that hold a site -- the batched voxelizer's.)
 __global__ void __launch_bounds__(256) brick_position_kernel(const int32_t *__restrict__ idx, int n, Grid g, int by, int bx,
                                                              const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ base,
+                                                             const uint32_t *__restrict__ bsum, long long words,
                                                              int32_t *__restrict__ pos_to_row, int32_t *__restrict__ coords_out) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;            // canonical row = its rank
     if (j >= n) return;
@@ -577,13 +573,13 @@ __global__ void __launch_bounds__(256) brick_position_kernel(const int32_t *__re
     const long long cells = (long long)g.b * g.d * g.h * g.w;
     const int y0 = (q.z / by) * by, y1 = y0 + by < g.h ? y0 + by : g.h;
     const int xb0 = (q.w / bx) * bx, xb1 = xb0 + bx;
-    uint32_t line0 = rank_before(bitmap, base, g.key(q.x, q.y, y0, 0), cells, (uint32_t)n);
+    uint32_t line0 = index_rank_before(bitmap, base, bsum, words, g.key(q.x, q.y, y0, 0), cells, (uint32_t)n);
     uint32_t pos = line0;
     for (int yy = y0; yy < y1; ++yy) {
-        const uint32_t next0 = rank_before(bitmap, base, g.key(q.x, q.y, yy, 0) + g.w, cells, (uint32_t)n);     // start of the next line
-        const uint32_t a = xb0 > 0 ? rank_before(bitmap, base, g.key(q.x, q.y, yy, xb0), cells, (uint32_t)n) : line0;
+        const uint32_t next0 = index_rank_before(bitmap, base, bsum, words, g.key(q.x, q.y, yy, 0) + g.w, cells, (uint32_t)n);     // start of the next line
+        const uint32_t a = xb0 > 0 ? index_rank_before(bitmap, base, bsum, words, g.key(q.x, q.y, yy, xb0), cells, (uint32_t)n) : line0;
         pos += a - line0;
-        if (yy < q.z) pos += (xb1 < g.w ? rank_before(bitmap, base, g.key(q.x, q.y, yy, xb1), cells, (uint32_t)n) : next0) - a;
+        if (yy < q.z) pos += (xb1 < g.w ? index_rank_before(bitmap, base, bsum, words, g.key(q.x, q.y, yy, xb1), cells, (uint32_t)n) : next0) - a;
         else if (yy == q.z) pos += (uint32_t)j - a;
         line0 = next0;
     }
@@ -646,7 +642,8 @@ extern "C" int cpd_order_rows_bricks(const int32_t *indices, int n, int batch, c
     IndexView v = index_carve(const_cast<void *>(index), batch, shape_zyx, 1);
     Grid g{batch, shape_zyx[0], shape_zyx[1], shape_zyx[2]};
     // (the index must be the CANONICAL one of `indices`: row = rank)
-    brick_position_kernel<<<cpd_div_up(n, 256), 256, 0, s>>>(indices, n, g, brick_y, brick_x, v.bitmap, v.base, pos_to_row, coords_b);
+    brick_position_kernel<<<cpd_div_up(n, 256), 256, 0, s>>>(indices, n, g, brick_y, brick_x, v.bitmap, v.base, v.bsum, v.words, pos_to_row,
+                                                             coords_b);
     // then, inside every tile of 128 rows of that order, rows sorted by their 27-bit neighbour pattern (what cpd_order_rows_by_taps
     // does per 4096-row chunk): the kernels' 16-row tap skipping gets nearly uniform groups, the tile keeps its footprint
     rulebook_kernel<true><<<cpd_div_up(n, 256), 256, 0, s>>>(coords_b, n, g, 3, 3, 3, 1, 1, 1, 1, 1, 1, v.bitmap, v.base, v.perm, v.flags,

@@ -56,4 +56,29 @@ __device__ __forceinline__ int32_t site_lookup(const uint64_t *__restrict__ bitm
     return perm ? perm[r] : r;
 }
 
+// ---- what a consumer may read (the index contract) -----------------------------------------------------------------------
+// bitmap[w]  every word, always: the builders zero the whole bitmap first.
+// bsum[b]    the number of sites before scan block b (SCAN_TILE words), every block, always.
+// base[w]    the number of sites before word w -- defined for the words of a scan block that holds at least one site. An index
+//            the batched voxelizer leaves behind (cpd_voxelize_batch_index / _canonical / _frames) has NO prefix entries for
+//            blocks without a site: its scan visits touched blocks only (device_scan_touched); cpd_index_build and
+//            cpd_conv_outset write all of them.
+// So: a LOOKUP (site_lookup, the rulebook kernels) may use base[w] after it has found a bit in bitmap[w]; a RANK query at an
+// arbitrary cell -- "how many sites lie before this key", whether or not the cell is occupied -- goes through index_rank_before,
+// which answers from bsum[] where the word's block is empty. `n_total` is the index's site count (what the rank is past the
+// last cell, and what closes the last block: the full scan leaves no total behind bsum[]).
+__device__ __forceinline__ uint32_t index_rank_before(const uint64_t *__restrict__ bitmap, const uint32_t *__restrict__ base,
+                                                      const uint32_t *__restrict__ bsum, long long words, long long key,
+                                                      long long cells, uint32_t n_total) {
+    if (key >= cells) return n_total;
+    const long long wi = key >> 6;
+    const uint64_t w = bitmap[wi];
+    if (w == 0) {
+        const long long b = wi / SCAN_TILE, nb = (words + SCAN_TILE - 1) / SCAN_TILE;
+        const uint32_t start = bsum[b], next = b + 1 < nb ? bsum[b + 1] : n_total;
+        if (next == start) return start;             // a block without sites: the rank anywhere inside it is the count at its start
+    }
+    return base[wi] + (uint32_t)__popcll(w & ((1ull << (key & 63)) - 1ull));
+}
+
 }  // namespace
