@@ -162,6 +162,8 @@ SIGNATURES = {
     "cpd_anchor_loss_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_anchor_loss": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _F, _FP, _F, _F, _F, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_rcnn_loss": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _I, _FP, _F, _F, _F, _I, _VP, _VP, _VP, _VP]),
+    "cpd_rcnn_proto_loss": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _FP, _F, _F, _F, _F, _F, _I,
+                                 _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cpd_kitti_overlaps": (_I, [_I, _I, _VP, _VP, _VP, _VP, _VP, _I, ctypes.c_int64, _VP, _VP]),
     "cpd_kitti_match_workspace_bytes": (_SZ, [_I, _I, _I]),
     "cpd_kitti_match_scores": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),

@@ -273,7 +273,7 @@ class FusedLoss(torch.autograd.Function):
     """A loss computed together with its gradient by one kernel: forward returns (total as a 0-dim tensor, the kernel's loss vector,
     non-differentiable); backward hands the saved gradients on, scaled by the incoming one. `fn()` -> (losses, grads...) with one
     gradient per tensor of `inputs`, shaped like it (None for an input given as None). Used by the fused loss kernels
-    (cpd_anchor_loss, cpd_rcnn_loss)."""
+    (cpd_anchor_loss, cpd_rcnn_loss, cpd_rcnn_proto_loss)."""
 
     @staticmethod
     def forward(ctx, fn, *inputs):

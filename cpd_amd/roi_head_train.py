@@ -9,7 +9,8 @@ canonical transformation, RoI losses and the prototype ("MM") pooling branch.
 
 Where the work is: the RoI x GT 3-D IoU matrices (`cpd_boxes_iou3d`), proposal NMS (`cpd_nms_batch`), the neighbour queries and
 the differentiable grouping (`cpd_voxel_query*`, `cpd_group_points`, `cpd_group_points_grad`) are C-ABI kernels; the FC stacks,
-BatchNorm with batch statistics and the loss formulas are torch ops on the device, as they are in the reference. The branches
+BatchNorm with batch statistics and the loss formulas are torch ops on the device, as they are in the reference (with
+`VoxelRCNNProtoHead.fused_loss` the loss and its gradient are one `cpd_rcnn_proto_loss` launch instead). The branches
 built are the ones the shipped config selects (voxel_rcnn_cproto_center.yaml: CLS_SCORE_TYPE roi_iou or cls, scalar thresholds,
 BinaryCrossEntropy, smooth-l1, corner regularisation); the per-class threshold variants (roi_iou_x / roi_ioud*) raise.
 The sampler draws its random numbers with the same calls in the same order as the reference (np.random.permutation / rand,
@@ -161,6 +162,12 @@ def rcnn_head_loss_torch(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, r
     return total + bb, terms
 
 
+def _kernel_rows(t, n, flat=False):
+    """A loss input as the kernels read it: n contiguous fp32 rows ([n] when `flat`), detached."""
+    t = t.detach().reshape(n) if flat else t.detach().reshape(n, t.shape[-1])
+    return t.float().contiguous()
+
+
 def rcnn_loss_fused(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, code_weights,
                     cls_weight=1.0, reg_weight=1.0, corner_weight=1.0, corner_regularization=True):
     """`cpd_rcnn_loss`: the loss of rcnn_head_loss_torch and its gradient in one launch, nothing read back.
@@ -168,10 +175,7 @@ def rcnn_loss_fused(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_va
     from ._lib import check, farr, lib, ptr, stream
     n = rcnn_reg.numel() // 7
     dev = rcnn_reg.device
-
-    def rows(t, flat=False):
-        t = t.detach().reshape(n) if flat else t.detach().reshape(n, t.shape[-1])
-        return t.float().contiguous()
+    rows = lambda t, flat=False: _kernel_rows(t, n, flat)
     cls, reg = rows(rcnn_cls, True), rows(rcnn_reg)
     roi = rows(rois)[:, 0:7].contiguous()
     gt, src = rows(gt_of_rois), rows(gt_of_rois_src)
@@ -193,6 +197,122 @@ def rcnn_head_loss(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_val
         return rcnn_loss_fused(rcnn_cls, rcnn_reg, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, code_weights,
                                cls_weight, reg_weight, corner_weight, corner_regularization)
     return FusedLoss.apply(fn, rcnn_cls, rcnn_reg)
+
+
+# ------------------------------------------------------------------------------------------------ the prototype head's loss
+RAMP_BEGIN, RAMP_END, RAMP_ITERS = 0.00001, 0.2, 5000              # proto_loss's ramp (voxel_rcnn_head.py:429-435)
+
+
+def proto_ramp_weight(it):
+    """The weight proto_loss gives its prototype terms at iteration `it` (counted from 1, clamped at RAMP_ITERS)."""
+    return (min(it, RAMP_ITERS) / RAMP_ITERS) * (RAMP_END - RAMP_BEGIN) + RAMP_BEGIN
+
+
+PROTO_TERMS = ("total", "cls0", "reg0", "corner0", "cls1", "reg1", "corner1", "b0", "b1", "feat", "Fc", "Fp")
+
+
+def proto_head_loss_torch(cls0, reg0, feat0, cls1, reg1, feat1, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels,
+                          css_score, code_weights, cls_weight=1.0, reg_weight=1.0, corner_weight=1.0, proto_weight=1.0,
+                          ramp_weight=RAMP_END, corner_regularization=True):
+    """VoxelRCNNProtoHead.get_loss (voxel_rcnn_head.py:388-579: get_box_cls_layer_loss and get_box_reg_layer_loss on both branches,
+    proto_loss) as one function of its inputs, in torch on the helpers above -- the restatement `cpd_rcnn_proto_loss` is tested
+    against, itself pinned on the reference's output (tests/golden/proto_loss.npz). Branch 0 is the detection branch, branch 1 the
+    prototype branch; the target rows (rois ... css_score, flattened to N rows) serve both; `ramp_weight` is proto_loss's weight at
+    the current iteration (proto_ramp_weight(iter)). Differentiable in cls0 / reg0 / feat0 / cls1 / reg1; feat1 and the boxes decoded
+    from reg1 are constants of the prototype terms.
+    -> (total, terms): terms[k] for k in PROTO_TERMS, tensors but Fc / Fp (ints); the branch terms before the 0.5 and proto_weight
+    factors, b1 and feat after their ramp factors, corner_j zero when the corner term is absent."""
+    labels = rcnn_cls_labels.reshape(-1).float()
+    n = labels.shape[0]
+    css = css_score.reshape(-1).float()
+    valid = (labels >= 0).float()
+    gt_ct = gt_of_rois.reshape(n, -1)[:, 0:7].clone()
+    # encode_torch clamps the gt's sizes IN PLACE (box_coder_utils.py:23, on a view of targets_dict0['gt_of_rois']): proto_loss, which
+    # runs after the regression losses, reads them clamped
+    gt_ct[:, 3:6] = gt_ct[:, 3:6].clamp_min(1e-5)
+    gt_src = gt_of_rois_src.reshape(n, -1)[:, 0:7]
+    roi = rois.reshape(n, -1)[:, 0:7].detach()
+    fgp = reg_valid_mask.reshape(-1) > 0
+    fgc = reg_valid_mask.reshape(-1) * css > 0
+    n_fgp, n_fgc = int(fgp.long().sum()), int(fgc.long().sum())
+    local = roi.clone()
+    local[:, 0:3] = 0
+    local[:, 6] = 0
+    target = residual_encode(gt_ct, local)
+    cw = torch.as_tensor(code_weights, dtype=torch.float32, device=roi.device).view(1, -1)
+    # (the ignored rows go in as 0: torch rejects targets outside [0, 1]; their terms are masked out, as in the reference)
+    bce_target = torch.where(labels >= 0, labels, torch.zeros_like(labels))
+
+    def branch(cls, reg):
+        bce = F.binary_cross_entropy(torch.sigmoid(cls.reshape(-1)), bce_target, reduction="none")
+        cls_loss = (bce * (valid * css)).sum() / torch.clamp(valid.sum(), min=1.0) * cls_weight
+        reg = reg.reshape(n, -1)
+        sl1 = smooth_l1((reg - torch.where(torch.isnan(target), reg, target)) * cw, 1.0 / 9.0)
+        reg_loss = (sl1 * fgc.unsqueeze(-1).float()).sum() / max(n_fgc, 1) * reg_weight
+        corner = reg.new_zeros(())
+        if corner_regularization and n_fgc > 0:
+            fg_roi = roi[fgc]
+            anchors = fg_roi.clone()
+            anchors[:, 0:3] = 0
+            boxes = residual_decode(reg[fgc], anchors)
+            boxes = rotate_points_along_z(boxes.unsqueeze(1), fg_roi[:, 6]).squeeze(1)
+            boxes = torch.cat([boxes[:, 0:3] + fg_roi[:, 0:3], boxes[:, 3:]], dim=-1)
+            corner = corner_loss_lidar(boxes[:, 0:7], gt_src[fgc]).mean() * corner_weight
+        return cls_loss, reg_loss, corner
+    c0, r0, k0 = branch(cls0, reg0)
+    c1, r1, k1 = branch(cls1, reg1)
+    w = float(ramp_weight)
+    p0, p1 = residual_decode(reg0.reshape(n, -1), local), residual_decode(reg1.reshape(n, -1), local).detach()
+    b0 = b1 = p0.new_zeros(())
+    if n_fgp > 0:
+        b0 = (bb_loss(p0[fgp], gt_ct[fgp]) * css[fgp]).sum() / (n_fgp + 1)
+        b1 = (bb_loss(p0[fgp], p1[fgp]) * css[fgp]).sum() / (n_fgp + 1) * w * w        # ramped twice (l.438, 454)
+    sim = -torch.cosine_similarity(feat0.reshape(n, -1), feat1.reshape(n, -1).detach(), dim=-1)
+    feat = (sim * (valid * css)).sum() / torch.clamp((valid * css).sum(), min=1.0) * w
+    total = c0 + (r0 + k0) + (0.5 * c1 + 0.5 * (r1 + k1) + (b0 + b1 + feat)) * proto_weight
+    return total, dict(zip(PROTO_TERMS, (total, c0, r0, k0, c1, r1, k1, b0, b1, feat, n_fgc, n_fgp)))
+
+
+def proto_loss_fused(cls0, reg0, feat0, cls1, reg1, feat1, rois, gt_of_rois, gt_of_rois_src, reg_valid_mask, rcnn_cls_labels, css_score,
+                     code_weights, cls_weight=1.0, reg_weight=1.0, corner_weight=1.0, proto_weight=1.0, ramp_weight=RAMP_END,
+                     corner_regularization=True):
+    """`cpd_rcnn_proto_loss`: the loss of proto_head_loss_torch and its gradient in one launch, nothing read back.
+    -> (losses [12] in PROTO_TERMS' order on the device, d_cls0, d_reg0, d_feat0, d_cls1, d_reg1 shaped like their inputs)."""
+    from ._lib import check, farr, lib, ptr, stream
+    n = reg0.numel() // 7
+    rows = lambda t, flat=False: _kernel_rows(t, n, flat)
+    c0, r0, f0, c1, r1, f1 = rows(cls0, True), rows(reg0), rows(feat0), rows(cls1, True), rows(reg1), rows(feat1)
+    roi = rows(rois)[:, 0:7].contiguous()
+    gt, src = rows(gt_of_rois), rows(gt_of_rois_src)
+    mask, labels, css = rows(reg_valid_mask, True), rows(rcnn_cls_labels, True), rows(css_score, True)
+    assert r0.shape[1] == 7 and r1.shape == r0.shape and f1.shape == f0.shape and gt.shape[1] >= 7 and src.shape[1] >= 7, \
+        (r0.shape, r1.shape, f0.shape, f1.shape, gt.shape, src.shape)
+    d_c0, d_r0, d_f0, d_c1, d_r1 = (torch.empty_like(t) for t in (c0, r0, f0, c1, r1))
+    losses = torch.empty(len(PROTO_TERMS), dtype=torch.float32, device=r0.device)
+    check(lib().cpd_rcnn_proto_loss(ptr(c0), ptr(r0), ptr(f0), ptr(c1), ptr(r1), ptr(f1), f0.shape[1], ptr(roi), ptr(gt), gt.shape[1], ptr(src),
+                                    src.shape[1], ptr(mask), ptr(labels), ptr(css), n, farr([float(v) for v in code_weights]),
+                                    float(cls_weight), float(reg_weight), float(corner_weight), float(proto_weight), float(ramp_weight),
+                                    int(bool(corner_regularization)), ptr(d_c0), ptr(d_r0), ptr(d_f0), ptr(d_c1), ptr(d_r1), ptr(losses),
+                                    stream()), "cpd_rcnn_proto_loss")
+    return losses, d_c0.view(cls0.shape), d_r0.view(reg0.shape), d_f0.view(feat0.shape), d_c1.view(cls1.shape), d_r1.view(reg1.shape)
+
+
+def proto_head_loss(cls0, reg0, feat0, cls1, reg1, feat1, *targets, **weights):
+    """proto_head_loss_torch (same arguments) through `cpd_rcnn_proto_loss`, differentiable in cls0 / reg0 / feat0 / cls1 / reg1 (the
+    gradient is the kernel's, saved by the forward). -> (total [0-dim], losses [12] in PROTO_TERMS' order on the device)."""
+    def fn():
+        return proto_loss_fused(cls0, reg0, feat0, cls1, reg1, feat1, *targets, **weights)
+    return FusedLoss.apply(fn, cls0, reg0, feat0, cls1, reg1)
+
+
+def set_fused_loss(model, on=True):
+    """Flip `fused_loss` on every VoxelRCNNProtoHead of `model`; returns how many there were."""
+    n = 0
+    for mod in model.modules():
+        if isinstance(mod, VoxelRCNNProtoHead):
+            mod.fused_loss = bool(on)
+            n += 1
+    return n
 
 
 # ------------------------------------------------------------------------------------------------ proposal target layer
@@ -400,7 +520,9 @@ def _fc_stack(pre, widths, dp, final=None, dropout_between=True):
 
 class VoxelRCNNProtoHead(nn.Module):
     """Same constructor arguments, parameter names and batch_dict contract as the reference class. `forward` in training mode
-    fills `forward_ret_dict['targets_dict0' / 'targets_dict1']`; `get_loss()` returns (rcnn_loss, tb_dict)."""
+    fills `forward_ret_dict['targets_dict0' / 'targets_dict1']`; `get_loss()` returns (rcnn_loss, tb_dict).
+    `fused_loss` (default False; set_fused_loss flips it on a whole model): get_loss runs as ONE `cpd_rcnn_proto_loss` launch that
+    yields the loss and its gradient, with one read-back (tb_dict); the device loss vector stays in `last_losses`."""
 
     def __init__(self, input_channels, model_cfg, point_cloud_range=None, voxel_size=None, num_frames=1, num_class=1, **kwargs):
         super().__init__()
@@ -432,6 +554,8 @@ class VoxelRCNNProtoHead(nn.Module):
         self.register_buffer("code_weights", torch.tensor(cw, dtype=torch.float32), persistent=False)
         self.forward_ret_dict = {}
         self.iter = 1
+        self.fused_loss = False
+        self.last_losses = None
         self.init_weights()
 
     def init_weights(self):
@@ -538,6 +662,13 @@ class VoxelRCNNProtoHead(nn.Module):
             tb["rcnn_loss_corner"] = corner.item()
         return loss, tb
 
+    def _next_ramp_weight(self):
+        """l.429-436: this iteration's weight of the prototype terms; `iter` is clamped, then advanced."""
+        self.iter = min(self.iter, RAMP_ITERS)
+        w = proto_ramp_weight(self.iter)
+        self.iter += 1
+        return w
+
     def proto_loss(self, t0, t1):
         """l.388-459: the detection branch is pulled towards its canonical ground truth and towards the (detached) prototype
         branch, in box space (bb_loss) and in feature space (cosine similarity), ramped up over the first 5000 iterations."""
@@ -557,10 +688,7 @@ class VoxelRCNNProtoHead(nn.Module):
         else:
             b0 = (bb_loss(p0[fg], gt_ct[fg]) * css[fg]).sum() / (fg.sum() + 1)
             b1 = (bb_loss(p0[fg], p1[fg]) * css[fg]).sum() / (fg.sum() + 1)
-        begin, end, max_iter = 0.00001, 0.2, 5000
-        self.iter = min(self.iter, max_iter)
-        w = (self.iter / max_iter) * (end - begin) + begin
-        self.iter += 1
+        w = self._next_ramp_weight()
         b1 = b1 * w
         sim = -torch.cosine_similarity(t0["shared_features"], t1["shared_features"].clone().detach(), dim=-1)
         valid = (t0["rcnn_cls_labels"].view(-1) >= 0).float() * css
@@ -571,6 +699,21 @@ class VoxelRCNNProtoHead(nn.Module):
         """l.556-579."""
         tb_dict = {} if tb_dict is None else tb_dict
         t0, t1 = self.forward_ret_dict["targets_dict0"], self.forward_ret_dict["targets_dict1"]
+        if self.fused_loss:
+            lc = self.model_cfg["LOSS_CONFIG"]
+            if lc["CLS_LOSS"] != "BinaryCrossEntropy":
+                raise NotImplementedError(lc["CLS_LOSS"])
+            if lc["REG_LOSS"] != "smooth-l1":
+                raise NotImplementedError(lc["REG_LOSS"])
+            lw = lc["LOSS_WEIGHTS"]
+            loss, self.last_losses = proto_head_loss(
+                t0["rcnn_cls"], t0["rcnn_reg"], t0["shared_features"], t1["rcnn_cls"], t1["rcnn_reg"], t1["shared_features"], t0["rois"],
+                t0["gt_of_rois"], t0["gt_of_rois_src"], t0["reg_valid_mask"], t0["rcnn_cls_labels"], t0["additional_data"]["css_score"],
+                lw["code_weights"], cls_weight=lw["rcnn_cls_weight"], reg_weight=lw["rcnn_reg_weight"], corner_weight=lw["rcnn_corner_weight"],
+                proto_weight=lw["rcnn_proto_weight"], ramp_weight=self._next_ramp_weight(),
+                corner_regularization=bool(lc["CORNER_LOSS_REGULARIZATION"]))
+            tb_dict["rcnn_loss"] = loss.item()
+            return loss, tb_dict
         cls0, _ = self.get_box_cls_layer_loss(t0)
         reg0, _ = self.get_box_reg_layer_loss(t0)
         cls1, _ = self.get_box_cls_layer_loss(t1)

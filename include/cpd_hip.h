@@ -736,6 +736,31 @@ int cpd_rcnn_loss(const float *rcnn_cls, const float *rcnn_reg, const float *roi
                   const float *gt_of_rois_src, int ld_src, const float *reg_valid_mask, const float *rcnn_cls_labels, int n,
                   const float code_weights[7], float cls_weight, float reg_weight, float corner_weight,
                   int corner_regularization, float *d_cls, float *d_reg, float *losses, cpd_stream_t stream);
+/* VoxelRCNNProtoHead.get_loss (voxel_rcnn_head.py:388-579: two get_box_cls_layer_loss, two get_box_reg_layer_loss, proto_loss) fused
+ * with its gradient, for n RoI rows. Branch 0 is the detection branch, branch 1 the prototype branch: cls0 / cls1 [n], reg0 / reg1
+ * [n][7], feat0 / feat1 [n][feat_dim] (the shared features, feat_dim >= 1). The target rows serve both branches and are
+ * cpd_rcnn_loss's, plus css_score [n], the prototype confidence. With valid = label >= 0, V = #valid, fgp = mask > 0, Fp = #fgp,
+ * fgc = mask x css > 0, Fc = #fgc, Sv = sum valid x css:
+ *   cls_j    = cls_weight x sum valid x css x BCE(sigmoid(cls_j), label) / max(V, 1)        (the css weights the numerator only)
+ *   reg_j    = reg_weight x sum over fgc of smooth-L1 (beta 1/9, code_weights) / max(Fc, 1)  (cpd_rcnn_loss's targets, NaN rule)
+ *   corner_j = corner_weight x mean over fgc of get_corner_loss_lidar                        (corner_regularization and Fc > 0)
+ *   b0       = sum over fgp of css x bb_loss(p0, canonical gt, sizes clamp_min 1e-5) / (Fp + 1), 0 when Fp = 0; p_j = reg_j decoded
+ *              against the RoI with xyz and heading zeroed
+ *   b1       = ramp_weight^2 x sum over fgp of css x bb_loss(p0, p1) / (Fp + 1), p1 a constant (the reference ramps it twice)
+ *   feat     = ramp_weight x sum valid x css x (-cos(feat0, feat1)) / max(Sv, 1), feat1 a constant; cos is torch.cosine_similarity:
+ *              sum (x / max(|x|, 1e-8)) (y / max(|y|, 1e-8)), whose backward passes through the norm below the bound too (the clamp is
+ *              outside the graph) and gives the norm no gradient at a zero vector
+ *   total    = cls0 + reg0 + corner0 + proto_weight x (0.5 cls1 + 0.5 (reg1 + corner1) + b0 + b1 + feat)
+ * Writes d(total)/d(cls0, reg0, feat0, cls1, reg1) (feat1 and p1 get none; d_feat0 is zero on rows of zero weight) and
+ * losses[12] = {total, cls0, reg0, corner0, cls1, reg1, corner1, b0, b1, feat, Fc, Fp} on the device: the branch terms before the
+ * 0.5 and proto_weight factors, b1 and feat after their ramp factors. One launch, one workgroup, no workspace, nothing read back;
+ * deterministic (fixed-order sums, no atomics). n = 0 writes zero losses (the row pointers may then be NULL).                      */
+int cpd_rcnn_proto_loss(const float *cls0, const float *reg0, const float *feat0, const float *cls1, const float *reg1,
+                        const float *feat1, int feat_dim, const float *rois, const float *gt_of_rois, int ld_gt,
+                        const float *gt_of_rois_src, int ld_src, const float *reg_valid_mask, const float *rcnn_cls_labels,
+                        const float *css_score, int n, const float code_weights[7], float cls_weight, float reg_weight,
+                        float corner_weight, float proto_weight, float ramp_weight, int corner_regularization, float *d_cls0,
+                        float *d_reg0, float *d_feat0, float *d_cls1, float *d_reg1, float *losses, cpd_stream_t stream);
 /* Adam with decoupled weight decay on a flat buffer (tools/train_utils/optimization/fastai_optim.py:
  * 132-150 true_wd semantics): grad is multiplied first by grad_scale (1/world after all-reduce) and,
  * when grad_scale_dev is not NULL, by the float it points to in device memory (the clip factor of
