@@ -29,6 +29,7 @@ class AnchorPointEngine(CenterPointEngine):
                  device="cuda", host_results=False):
         self.head_cfg, self.nms_cfg, self.class_names = head_cfg, nms_cfg, list(class_names)
         self.proposal_first_rows = None       # candidates per frame the proposal NMS looks at first (None: max(512, 4 * NMS_POST_MAXSIZE))
+        self.proposal_full_reruns = 0         # steps whose survivors were not all among those candidates: the full NMS ran as well
         super().__init__(cfg, state_dict, device=device, host_results=host_results)
         if nms_cfg.get("MULTI_CLASSES_NMS", False) or nms_cfg["NMS_TYPE"] != "nms_gpu":
             raise NotImplementedError("proposal NMS variant not selected by the shipped CPD configs")
@@ -87,17 +88,12 @@ class AnchorPointEngine(CenterPointEngine):
         tail = [inc.max().view(1)] + ([flag] if flag is not None else [])
         ns = torch.cat([kept.to(torch.int32)] + tail).tolist()                                       # the stage's one read-back
         if ns[batch]:                                    # some frame needs boxes beyond its first `rows`: the full NMS, once more
-            self.proposal_full_reruns = getattr(self, "proposal_full_reruns", 0) + 1
+            self.proposal_full_reruns += 1
             rois, scores, labels, kept = roi_pool.proposal_layer(boxes, cls, float(nms["NMS_THRESH"]), int(nms["NMS_PRE_MAXSIZE"]), post)
             ns[:batch] = kept.tolist()
         del ns[batch]
-        high = bool(ns[batch]) if flag is not None else False
-        if getattr(self, "_rb_scaled", False):
-            self._range_exceeded, self._range_high = False, high
-        else:
-            self._range_exceeded = high
-        if self._range_exceeded:
-            return None
+        if self.guard.verdict(flag is not None and ns[batch]):
+            return None                                  # forward() runs the step again, guarded
         return rois, scores, labels, [int(v) for v in ns[:batch]]
 
     @torch.no_grad()

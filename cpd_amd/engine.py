@@ -18,6 +18,7 @@ import torch
 
 from . import _lib, layer_table, ops, train_ops
 from .layer_table import _DOWN, STRIDED_STAGES, final_shape      # noqa: F401  (_DOWN: importable from here as before)
+from .range_guard import GUARDED_BITS, OPTIMISTIC_BITS, BlockPool, RangeGuard
 
 
 @dataclass
@@ -309,6 +310,18 @@ class CenterPointEngine:
         self.last_head_at_peaks = False    # did the last step evaluate the regression branches at the peaks only (diagnostics, tests)
         self._peaks = None                 # (a CenterHead's layers cut at the peaks, _build_head; other dense heads leave it None)
         self.head_at_peaks = bool(cfg.head_at_peaks) and os.environ.get("CPD_HEAD_AT_PEAKS", "1") != "0"
+        self.guard = RangeGuard(self.RANGE_STICKY_STEPS)
+        self._pool = None                  # the step's absmax blocks; None: nothing is recorded (another arithmetic, or the guard switched off)
+        if cfg.conv_math == "f16x2" and cfg.range_guard:
+            self._pool = BlockPool("range guard: this model launches more convolutions per step than the %d absmax blocks the engine "
+                                   "sized from its config (engine._range_reset)")
+        self._range_new = self._pool.new_block if self._pool is not None else (lambda: None)     # the block of one conv launch
+        self._rb = None                    # block of the tensor the NEXT conv reads (_conv)
+        self._rb_stage = None              # "backbone" between backbone3d and the bev_and_head that goes on from its blocks
+        self._dense_map = None             # the persistent BEV map of the step in flight, until its one reader is queued
+        self._export_pair_levels = False   # forward(pair_levels=True): exported levels stay fp16-pair rows
+        self.encoded_pairs = False         # did the last backbone3d leave its stride-8 output in pair rows
+        self._index_chain = None           # the step's StridedStageChain (held until the next step replaces it)
         self._build_layers()
 
     # ------------------------------------------------------------------ weights
@@ -363,52 +376,34 @@ class CenterPointEngine:
         return _lib.side_stream(self.device, "index")      # (per current stream: an engine may be driven from several streams over its life)
 
     # ------------------------------------------------------------------ forward pieces
-    # Range guard of the f16x2 path. Every conv epilogue raises an absmax block to max |out| (a wave
-    # reduction + a rarely issued atomic: free). OPTIMISTIC pass: the layers run their unscaled kernels and only RECORD; the largest
-    # recorded value rides along with the step's final count read-back, and if any activation reached 2^15 the step is run again
-    # in the GUARDED mode, where each layer takes its input's block as `in_absmax` (the `*_f16s_*` kernels pre-scale by a power of
-    # two: exact at any magnitude). Always guarded costs the dense kernels ~3 % (the extra multiply in their staging); a re-run
-    # costs a step, once, for inputs the unguarded arithmetic would have turned into inf / NaN (or, behind a ReLU, into zeros).
+    # Range guard of the f16x2 path (range_guard.py). Every conv epilogue raises an absmax block of the step's pool to max |out| (a wave
+    # reduction + a rarely issued atomic: free). OPTIMISTIC pass: the layers run their unscaled kernels and only RECORD. GUARDED pass
+    # (guard.scaled): each layer also takes its input's block as `in_absmax` (the `*_f16s_*` kernels pre-scale by a power of two).
     # `self._rb` = block of the tensor the NEXT conv reads; a _conv call consumes it and replaces it by the block its epilogue fills.
     def _range_reset(self):
         self._rb = None
-        self._rb_next = 0
-        if self.cfg.conv_math == "f16x2" and self.cfg.range_guard:
-            if getattr(self, "_rb_pool", None) is None:
-                # one block per conv launch of a step: 20 sparse layers + conv_out, the BEV levels' convs, the concat buffer,
-                # shared conv + the two head launches (three with the head cut at the peaks; + slack for callers that run the stages on their own)
-                n = 21 + sum(k + 1 for k in self.cfg.bev_layer_nums) + 1 + 3 + 16
-                self._rb_pool = ops.absmax_blocks(n, self.device)
-            else:
-                self._rb_pool.zero_()
-        else:
-            self._rb_pool = None
-
-    def _range_new(self):
-        if self._rb_pool is None:
-            return None
-        if self._rb_next >= self._rb_pool.shape[0]:
-            raise RuntimeError("range guard: this model launches more convolutions per step than the %d absmax blocks the engine "
-                               "sized from its config (engine._range_reset)" % self._rb_pool.shape[0])
-        b = self._rb_pool[self._rb_next]
-        self._rb_next += 1
-        return b
+        if self._pool is not None:
+            # one block per conv launch of a step: 20 sparse layers + conv_out, the BEV levels' convs, the concat buffer,
+            # shared conv + the two head launches (three with the head cut at the peaks; + slack for callers that run the stages on their own)
+            self._pool.reset(21 + sum(k + 1 for k in self.cfg.bev_layer_nums) + 1 + 3 + 16, self.device)
 
     RANGE_STICKY_STEPS = 16       # guarded steps that follow a re-run before the engine tries the unguarded kernels again
+    range_reruns = property(lambda self: self.guard.reruns, lambda self, n: setattr(self.guard, "reruns", n))
+    range_guarded_steps = property(lambda self: self.guard.guarded_steps)
+    _guard_left = property(lambda self: self.guard.left)
 
     def _range_exceeded_flag(self):
         """device int32 [1] riding with the step's count read-back; None when nothing is recorded. Optimistic step: 1 when some
         recorded activation is >= 2^15 (or NaN / inf) -> the step is re-run guarded. Guarded step: 1 while some activation is
         still >= 2^14 -> the engine stays guarded (hysteresis: it returns to the unguarded kernels only after
         RANGE_STICKY_STEPS consecutive steps well inside fp16's range)."""
-        if self._rb_pool is None:
+        if self._pool is None:
             return None
-        thr = 0x46800000 if getattr(self, "_rb_scaled", False) else 0x47000000   # bits of 16384.0f / 32768.0f; NaN / inf bits are larger
-        return (self._rb_pool.max() >= thr).to(torch.int32).view(1)
+        return self._pool.flag(GUARDED_BITS if self.guard.scaled else OPTIMISTIC_BITS)
 
     def _conv(self, layer, x, nbr, n_out, residual=None, out=None, out_row_map=None, out_col_group=0, dense=False, out_rb="new",
               in_pairs=False, out_pairs=False, res_pairs=False):
-        rb_in = self._rb if getattr(self, "_rb_scaled", False) else None
+        rb_in = self._rb if self.guard.scaled else None
         rb_out = self._range_new() if out_rb == "new" else out_rb
         y = ops.gather_conv(x, layer.c_in, layer.w, nbr, layer.kv, n_out, layer.c_out, layer.scale, layer.shift,
                             residual, layer.relu, out=out, out_row_map=out_row_map, out_col_group=out_col_group,
@@ -489,7 +484,7 @@ class CenterPointEngine:
         # 16 matrix cycles instead of four fp32 MFMAs of 32); the 5-channel input layer stays on the fp32 pipe and writes the first pairs
         x = self._conv(L["conv_input"], feats, nbr, coords.shape[0], out_pairs=pairs16)
         x = self._blocks(L["conv1"], x, nbr, pairs=pairs16)
-        raw = getattr(self, "_export_pair_levels", False)     # exported levels stay fp16-pair rows, wrapped in ops.PairRows (the RoI pooling's first GEMM reads them as they are)
+        raw = self._export_pair_levels                        # exported levels stay fp16-pair rows, wrapped in ops.PairRows (the RoI pooling's first GEMM reads them as they are)
 
         def export(t, is_pairs, name):
             if not (is_pairs and want(name)):
@@ -581,7 +576,7 @@ class CenterPointEngine:
         cfg = self.cfg
         pk = dict(in_pairs=True, out_pairs=True) if pairs else {}
         T = bev_tables(self._bev_cache, batch, h, w, self.device)
-        if getattr(self, "_rb_stage", None) != "backbone":     # called on its own (tests, tools): the input's range is unknown
+        if self._rb_stage != "backbone":                       # called on its own (tests, tools): the input's range is unknown
             self._range_reset()
         self._rb_stage = None
         cat_rb = self._range_new()                             # ONE block for the concat buffer: both deblocks raise it
@@ -605,7 +600,7 @@ class CenterPointEngine:
                 raise NotImplementedError("BEV stride pattern outside the shipped configs")
             n_lvl = batch * ho * wo
             x = self._conv(convs[0], x, nbr0, n_lvl, dense=True, **pk)
-            if lvl == 0 and getattr(self, "_dense_map", None) is not None:
+            if lvl == 0 and self._dense_map is not None:
                 self._dense_map.clear()                        # the densified map's only reader is queued: its rows go back to zero
                 self._dense_map = None
             nbr_same = T["s1"][0] if (ho, wo) == (h, w) else T["s1_half"][0]
@@ -707,14 +702,9 @@ class CenterPointEngine:
         # MI355X / ROCm 7.2 -- tools/d2h_probe.py -- whatever the wait that followed them: event, stream or a later blocking read.)
         host = blk.cpu() if whole else None       # the one host read-back of the stage
         ns = (ops.unpack_boxes(host, lay)[0] if whole else hdr).tolist()
-        high = bool(ns[batch]) if flag is not None else False
-        if getattr(self, "_rb_scaled", False):
-            self._range_exceeded, self._range_high = False, high     # guarded already: exact whatever the range; `high` keeps it guarded
-        else:
-            self._range_exceeded = high
-        ns = ns[:batch]
-        if self._range_exceeded:
+        if self.guard.verdict(flag is not None and ns[batch]):
             return None                           # forward() runs the step again, guarded
+        ns = ns[:batch]
         if raw:                                   # the padded device block + per-frame counts (the two-stage engine's proposals)
             return ob, os_, ol, ns
         if whole:
@@ -781,21 +771,15 @@ class CenterPointEngine:
             ms = torch.cat([o[4] for o in outs]).tolist() if batch > 1 else [int(outs[0][4].item())]   # one read-back
             feats = torch.cat([o[3][:m] for o, m in zip(outs, ms)]) if batch > 1 else outs[0][3][:ms[0]]
             coords = torch.cat([o[1][:m] for o, m in zip(outs, ms)]) if batch > 1 else outs[0][1][:ms[0]]
-        # A step whose activations left fp16's safe range is re-run guarded (exact), and the engine then STAYS guarded for the next
-        # RANGE_STICKY_STEPS steps (each of which extends the stay while its activations are still >= 2^14): a checkpoint or scene
-        # that habitually exceeds the range pays the guarded kernels' ~3 % instead of a second pass per step.
-        self.range_reruns = getattr(self, "range_reruns", 0)
-        self.range_guarded_steps = getattr(self, "range_guarded_steps", 0)
-        self._guard_left = getattr(self, "_guard_left", 0)
-        self._rb_scaled = self._guard_left > 0
-        self._range_high = False
+        guard = self.guard
+        guard.begin_step()                                   # guarded from the start while the stay after a re-run lasts (range_guard.py)
         fd, fh, fw = self._final_shape()
         self._export_pair_levels = bool(pair_levels) and proposals is not None
         while True:
-            dp = (not self._rb_scaled) and self.dense_pairs_ok(batch, fh, fw)
+            dp = (not guard.scaled) and self.dense_pairs_ok(batch, fh, fw)
             levels, (x, out_idx, out_shape) = self.backbone3d(feats, coords, batch, index=index0, canonical0=canonical0,
                                                               export_levels=proposals if proposals is not None else return_intermediates,
-                                                              pair_rows=self.cfg.pair_rows and not self._rb_scaled, dense_pairs=dp)
+                                                              pair_rows=self.cfg.pair_rows and not guard.scaled, dense_pairs=dp)
             d, h, w = out_shape
             dp = dp and self.encoded_pairs
             # the BEV map: a persistent pre-zeroed buffer per batch shape -- the occupied rows (12 % at this level) are scattered in and,
@@ -817,18 +801,8 @@ class CenterPointEngine:
             results = self.decode_and_nms(head, batch, h, w, raw=proposals is not None)
             if results is not None:
                 break
-            # an activation left fp16's safe range: the same step with every layer pre-scaling its input (exact), see _range_reset
-            if self.range_reruns == 0:
-                import warnings
-                warnings.warn("cpd_amd: an activation reached 2^15 -- step re-run with the range-guarded f16x2 kernels; the engine "
-                              "stays guarded for the next %d steps" % self.RANGE_STICKY_STEPS)
-            self._rb_scaled = True
-            self.range_reruns += 1
-            self._guard_left = self.RANGE_STICKY_STEPS + 1
-        if self._rb_scaled:
-            self.range_guarded_steps += 1
-            self._guard_left = self.RANGE_STICKY_STEPS if self._range_high else self._guard_left - 1
-        self._rb_scaled = False
+            guard.trip()     # an activation left fp16's safe range: the same step with every layer pre-scaling its input (exact), range_guard.py
+        guard.end_step()
         if proposals is not None:
             return results + (levels,)
         if return_intermediates:

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import autograd_ops, iou3d_nms_utils, layer_table, ops, recall, train_ops
 from . import spconv as _spconv_pkg
+from .range_guard import RangeGuard
 from .spconv import pytorch as spconv
 from .spconv.pytorch import conv as _spc
 from .spconv.pytorch.conv import default_conv_math, fold_batchnorm as _fold_batchnorm, fusable_eval as _fusable_eval
@@ -874,6 +875,7 @@ class CenterPoint(nn.Module):
                                                        point_cloud_range=self.point_cloud_range, voxel_size=self.voxel_size,
                                                        predict_boxes_when_training=False)
         self.module_list = [self.vfe, self.backbone_3d, self.map_to_bev_module, self.backbone_2d, self.dense_head]
+        self.guard = RangeGuard(self.FAST_EVAL_STICKY_STEPS, "model")
 
     def forward(self, batch_dict):
         """centerpoint.py:9-22: training returns ({'loss': loss}, tb_dict, disp_dict) -- `loss.backward()` then reaches every
@@ -902,15 +904,19 @@ class CenterPoint(nn.Module):
         return rec.as_dict()
 
     FAST_EVAL_STICKY_STEPS = 16
+    range_reruns = property(lambda self: self.guard.reruns, lambda self, n: setattr(self.guard, "reruns", n))
+    _guard_left = property(lambda self: self.guard.left)
 
     def _run_modules(self, batch_dict):
         """module_list over the batch_dict. Fast eval (spconv.install(fast_eval=True), every module in eval(), no autograd, f16x2): the
         modules run inside an optimistic range pass -- unscaled split-fp16 kernels, fp16-pair rows between the fused sparse layers,
         max |activation| recorded --, the verdict is read once behind the last module, and a step with an activation >= 2^15 is run
-        AGAIN on the guarded kernels (exact at any magnitude); the model then stays guarded for FAST_EVAL_STICKY_STEPS steps, like
-        the engine (engine.RANGE_STICKY_STEPS)."""
+        AGAIN on the guarded kernels (exact at any magnitude); the model then stays guarded for FAST_EVAL_STICKY_STEPS steps
+        (range_guard.RangeGuard, as the engine's; a guarded module step reads no verdict, so the stay is never extended)."""
+        guard = self.guard
+        guard.begin_step()
         fast = (not self.training and _spc.fast_eval() and default_conv_math() == "f16x2" and _fusable_eval(self)
-                and getattr(self, "_guard_left", 0) <= 0)
+                and not guard.scaled)
         if fast:
             feats = batch_dict.get("voxel_features")
             fast = feats is not None and feats.is_cuda
@@ -920,18 +926,13 @@ class CenterPoint(nn.Module):
                 for m in self.module_list:
                     batch_dict = m(batch_dict)
                 flag = rp.exceeded()
-            if not int(flag.item()):
+            if not guard.verdict(int(flag.item())):
                 return batch_dict
-            import warnings
-            warnings.warn("cpd_amd: an activation reached 2^15 -- step re-run with the range-guarded f16x2 kernels; the model stays "
-                          "guarded for the next %d steps" % self.FAST_EVAL_STICKY_STEPS)
-            self.range_reruns = getattr(self, "range_reruns", 0) + 1
-            self._guard_left = self.FAST_EVAL_STICKY_STEPS + 1
+            guard.trip()
             batch_dict = src
-        if getattr(self, "_guard_left", 0) > 0:
-            self._guard_left -= 1
         for m in self.module_list:
             batch_dict = m(batch_dict)
+        guard.end_step()
         return batch_dict
 
     def to_engine_config(self):

@@ -4,11 +4,13 @@ kernel on the adjoint weights / rulebook, the weight gradient cpd_conv_wgrad), s
 reference checkpoints load (detector3d_template.py:388-419)."""
 import math
 import os
+import threading
 
 import torch
 import torch.nn as nn
 
 from ... import autograd_ops, ops, train_ops
+from ...range_guard import OPTIMISTIC_BITS, BlockPool
 from .core import SparseConvTensor
 from .modules import SparseModule
 
@@ -59,14 +61,16 @@ def default_row_order():
 #     bits as MFMA fragments) -- a SparseConvTensor then carries ops.PairRows and decodes `.features` only for a caller who reads it;
 #   * the OPTIMISTIC range guard: layers run their unscaled kernels and only RECORD max |out| into a pool of blocks; the detector
 #     (models.CenterPoint.forward) reads the pool's maximum with its results and runs the step again on the guarded kernels (fp32 rows,
-#     today's path) if an activation reached 2^15 -- exactly the engine's scheme (engine._range_reset).
+#     today's path) if an activation reached 2^15 -- the engine's scheme, on the same two classes (range_guard.py).
 # Outside a `range_pass` (a module called on its own, a custom detector) every layer stays guarded, as before.
 _FAST_EVAL = [os.environ.get("CPD_FAST_EVAL", "0") not in ("0", "", "false")]
-import threading as _threading
 
 
-class _RangeState(_threading.local):          # per thread: two batches in flight on two HIP streams (two worker threads) each own a pass
-    pool, next, active = None, 0, False
+class _RangeState(threading.local):           # per thread: two batches in flight on two HIP streams (two worker threads) each own a pass
+    active = False
+
+    def __init__(self):
+        self.pool = BlockPool("range_pass: more fused conv launches than the %d absmax blocks of the pass")
 
 
 _RANGE = _RangeState()
@@ -88,12 +92,8 @@ class range_pass:
         self.device, self.n = device, int(n_blocks)
 
     def __enter__(self):
-        pool = _RANGE.pool
-        if pool is None or pool.device != torch.device(self.device) or pool.shape[0] < self.n:
-            pool = _RANGE.pool = ops.absmax_blocks(self.n, self.device)
-        else:
-            pool.zero_()
-        _RANGE.next, _RANGE.active = 0, True
+        _RANGE.pool.reset(self.n, self.device)
+        _RANGE.active = True
         return self
 
     def __exit__(self, *exc):
@@ -101,7 +101,7 @@ class range_pass:
 
     @staticmethod
     def exceeded():
-        return (_RANGE.pool.max() >= 0x47000000).to(torch.int32).view(1)       # bits of 32768.0f; NaN / inf bits are larger
+        return _RANGE.pool.flag(OPTIMISTIC_BITS)
 
 
 def optimistic():
@@ -111,11 +111,7 @@ def optimistic():
 
 def record_block():
     """the next block of the active pass's pool (a layer's `out_absmax`)"""
-    if _RANGE.next >= _RANGE.pool.shape[0]:
-        raise RuntimeError("range_pass: more fused conv launches than the %d absmax blocks of the pass" % _RANGE.pool.shape[0])
-    b = _RANGE.pool[_RANGE.next]
-    _RANGE.next += 1
-    return b
+    return _RANGE.pool.new_block()
 
 
 def fold_batchnorm(bn, conv_bias=None):

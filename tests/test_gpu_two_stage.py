@@ -422,6 +422,31 @@ def test_anchor_two_stage_engine_matches_the_module_composition(hip):
     assert all(torch.isfinite(g["pred_boxes"]).all() for g in got2) and sum(len(g["pred_boxes"]) for g in got2) > 10
 
 
+def test_anchor_engine_reruns_an_out_of_range_step_guarded_and_stays_guarded(hip):
+    """The f16x2 range guard through AnchorPointEngine's own decode_and_nms (its verdict rides behind the proposal NMS's `incomplete`
+    word): a backbone running 3e4 times hotter, past 2^15, is flagged by the optimistic pass and re-run guarded, once, with a warning;
+    the next step starts guarded -- no second pass -- and gives the same proposals bit for bit. (conv_out's BatchNorm brings the dense half
+    back to ordinary magnitudes, as in test_gpu_head_at_peaks.py::test_range_guard_rerun_matches.)"""
+    from cpd_amd.anchor_engine import AnchorPointEngine
+    net = _anchor_model()
+    clouds = _clouds()
+    ecfg = net.to_engine_config()
+    ecfg.conv_math = "f16x2"
+    sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}
+    sd["backbone_3d.conv_input.1.weight"] = sd["backbone_3d.conv_input.1.weight"] * 3e4
+    sd["backbone_3d.conv_input.1.bias"] = sd["backbone_3d.conv_input.1.bias"] * 3e4
+    sd["backbone_3d.conv_out.1.weight"] = sd["backbone_3d.conv_out.1.weight"] / 3e4
+    rpn = AnchorPointEngine(ecfg, sd, net.model_cfg.DENSE_HEAD, net.model_cfg.ROI_HEAD.NMS_CONFIG["TEST"])
+    with pytest.warns(UserWarning, match="range-guarded"):
+        first = rpn.forward(clouds, proposals=["x_conv3", "x_conv4"])[:4]
+    assert (rpn.range_reruns, rpn.range_guarded_steps) == (1, 1)
+    again = rpn.forward(clouds, proposals=["x_conv3", "x_conv4"])[:4]
+    assert (rpn.range_reruns, rpn.range_guarded_steps) == (1, 2)
+    assert len(first[3]) == 3 and min(first[3]) > 0 and again[3] == first[3]
+    for a, b in zip(first[:3], again[:3]):
+        assert torch.isfinite(a.float()).all() and torch.equal(a, b)
+
+
 def _full_anchor_engine():
     """the model of bench.py's `value_two_stage_anchor`, from the same builder (cpd_amd.anchor_engine.synthetic_two_stage_state)"""
     from cpd_amd.anchor_engine import AnchorPointEngine, synthetic_two_stage_state
