@@ -207,6 +207,9 @@ SIGNATURES = {
                                _VP, _SZ, _VP]),
     "cpd_group_points_by_box_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_group_points_by_box": (_I, [_VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_tta_views": (_I, [_VP, ctypes.c_longlong, _I, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP]),
+    "cpd_tta_collect": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I] + [_VP] * 9 + [_VP]),
+    "cpd_tta_collect_cpu": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I] + [_VP] * 9),
 }
 
 

@@ -9,17 +9,11 @@
 // rounded once, the scaling is one float32 product by the factor rounded to float32 (np.random.uniform and a yaml number are
 // Python floats: numpy multiplies a float32 array by them in float32), the in-box test is the reference's fp32 / double expression (pt_in_box.h). The rotation is the one
 // place where a fused multiply-add is written, explicitly: torch's CPU float32 matmul of [1, N, 3] x [1, 3, 3] evaluates
-// fma(y, R[1][j], fl(x * R[0][j])) for all but tiny N.
+// fma(y, R[1][j], fl(x * R[0][j])) for all but tiny N. The op list and its arithmetic live in aug_ops.h, which tta.hip shares.
+#include "aug_ops.h"
 #include "pt_in_box.h"
 
 namespace {
-
-struct AugOps {
-    int n;
-    int kind[CPD_AUG_MAX_OPS];
-    float c[CPD_AUG_MAX_OPS], s[CPD_AUG_MAX_OPS];     // ROT: the host's float32 cos / sin
-    float f[CPD_AUG_MAX_OPS];                         // SCALE: the factor rounded to float32
-};
 
 struct AugRows {
     const float *scene;
@@ -49,25 +43,7 @@ struct AugRows {
         x = p[0]; y = p[1]; z = p[2];
         return p;
     }
-    __device__ __forceinline__ void apply(float &x, float &y, float &z) const {
-        for (int q = 0; q < ops.n; ++q) {
-            switch (ops.kind[q]) {
-            case CPD_AUG_FLIP_X: y = -y; break;
-            case CPD_AUG_FLIP_Y: x = -x; break;
-            case CPD_AUG_ROT: {
-                const float cs = ops.c[q], sn = ops.s[q];
-                const float nx = __fmaf_rn(y, -sn, __fmul_rn(x, cs));
-                const float ny = __fmaf_rn(y, cs, __fmul_rn(x, sn));
-                x = nx; y = ny;
-                break;
-            }
-            default: {                                   // CPD_AUG_SCALE: points[:, :3] *= Python float, a float32 product
-                const float f = ops.f[q];
-                x = __fmul_rn(x, f); y = __fmul_rn(y, f); z = __fmul_rn(z, f);
-            }
-            }
-        }
-    }
+    __device__ __forceinline__ void apply(float &x, float &y, float &z) const { aug_apply(ops, x, y, z); }     // (aug_ops.h)
     __device__ __forceinline__ bool in_range(float x, float y) const {      // false for NaN, as numpy's comparisons are
         return !has_range || (x >= x0 && x <= x1 && y >= y0 && y <= y1);
     }
@@ -281,14 +257,7 @@ extern "C" int cpd_augment_scene(const float *scene, int n, int c, const float *
         if (obj_start[s] + obj_count[s] > obj_rows) return CPD_ERR_ARG;
     if ((m > 0 && !obj_base) || (total > 0 && !out)) return CPD_ERR_ARG;
     AugRows r{};
-    for (int q = 0; q < n_ops; ++q) {
-        if (op_kind[q] < CPD_AUG_FLIP_X || op_kind[q] > CPD_AUG_SCALE) return CPD_ERR_ARG;
-        r.ops.kind[q] = op_kind[q];
-        r.ops.c[q] = (float)op_param[2 * q];
-        r.ops.s[q] = (float)op_param[2 * q + 1];
-        r.ops.f[q] = (float)op_param[2 * q];
-    }
-    r.ops.n = n_ops;
+    if (aug_ops_fill(r.ops, op_kind, op_param, n_ops) != CPD_OK) return CPD_ERR_ARG;
     const AugLayout l = augment_layout(total, k_obj);
     if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     hipStream_t s = cpd_s(st);

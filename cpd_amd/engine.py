@@ -322,6 +322,7 @@ class CenterPointEngine:
         self._export_pair_levels = False   # forward(pair_levels=True): exported levels stay fp16-pair rows
         self.encoded_pairs = False         # did the last backbone3d leave its stride-8 output in pair rows
         self._index_chain = None           # the step's StridedStageChain (held until the next step replaces it)
+        self.last_result_block = None      # (boxes [B, K, 7], scores, labels i64, counts i32 [B]) of the last step, on the device
         self._build_layers()
 
     # ------------------------------------------------------------------ weights
@@ -705,6 +706,7 @@ class CenterPointEngine:
         if self.guard.verdict(flag is not None and ns[batch]):
             return None                           # forward() runs the step again, guarded
         ns = ns[:batch]
+        self.last_result_block = (ob, os_, ol, on)     # the step's padded device block and its device counts (cpd_amd/tta.py goes on from it)
         if raw:                                   # the padded device block + per-frame counts (the two-stage engine's proposals)
             return ob, os_, ol, ns
         if whole:

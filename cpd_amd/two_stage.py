@@ -98,6 +98,7 @@ class VoxelRCNNEngine:
         keep, num_keep = ops.nms_batch(sboxes, n_ok, float(nms["NMS_THRESH"]))
         post = min(int(nms["NMS_POST_MAXSIZE"]), n_roi)
         fb, fs, fl, fn, blk = ops.select_boxes(sboxes, ranked, slabels, keep, num_keep, post, label_offset=0, packed=True)
+        self.last_result_block = (fb, fs, fl, fn)                        # the padded device block and its device counts (cpd_amd/tta.py)
         if recall is not None and gt_boxes is not None:                  # the padded final block and its device counts; every RoI slot
             recall.update(fb, None, fn, gt_boxes, rois=rois)
         if self.host_results:                                            # counts + boxes + scores + labels: one block, one copy

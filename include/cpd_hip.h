@@ -1268,6 +1268,54 @@ size_t cpd_group_points_by_box_workspace_bytes(int n, int k);
 int cpd_group_points_by_box(const float *points, int n, int c, const int32_t *box_idx, int k, const double *centre, float *out,
                             int32_t *offsets, void *workspace, size_t workspace_bytes, cpd_stream_t stream);
 
+/* ---- test-time augmentation around an engine step (csrc/tta.hip): TestAugmentor.forward of every view on a packed batch, and
+ * TestAugmentor.backward + DetectionsMerger's per-class floor and sort (merge_detections.py:195-207) on the views' result blocks.
+ * Both are queued on the stream and read nothing back.
+ *
+ * cpd_tta_views: points [n_total][c] f32 (c >= 3) = the frames of a batch one after the other, HOST frame_offsets [batch + 1] int64
+ * (first row of a frame; [0] = 0, ascending, [batch] = n_total). Per view v < n_views a HOST op list op_kind [n_views][CPD_AUG_MAX_OPS],
+ * op_param [n_views][CPD_AUG_MAX_OPS][2], n_ops [n_views], kinds and parameters as cpd_augment_scene takes them and applied by the same
+ * device function. out [n_views * n_total][c]: view v of frame f is rows v * n_total + frame_offsets[f] .. v * n_total +
+ * frame_offsets[f + 1] (view-major: v0f0, v0f1, .., v1f0, ..), the points in their order, columns >= 3 copied; no range filter, no
+ * compaction. CPD_ERR_ARG: n_views outside 1 .. CPD_TTA_MAX_VIEWS, n_ops[v] outside 0 .. CPD_AUG_MAX_OPS, an unknown op,
+ * n_views * n_total >= 2^31, offsets that are not as described, c < 3, a null pointer.
+ *
+ * cpd_tta_collect: the engine's results for the view-major batch as padded DEVICE blocks: boxes [n_views * batch][cap][7] f32, scores
+ * [n_views * batch][cap] f32, labels [n_views * batch][cap] i64 (1-based), counts [n_views * batch] i32 (rows past a count are not
+ * read). HOST: per view the REVERSED op queue as TestAugmentor.test_back_queue applies it to boxes: back_kind [n_views][CPD_AUG_MAX_OPS],
+ * back_param [n_views][CPD_AUG_MAX_OPS][3], n_back [n_views]: CPD_AUG_SCALE param[0] = WORLD_SCALE: columns 0-5 /= (float)scale, float32
+ * quotients; CPD_AUG_ROT param = (cos, sin, angle) of angle = -WORLD_ROT, cos / sin as the float32 values torch derives: x' = fl(fl(x cos)
+ * + fl(y (-sin))), y' = fl(fl(x sin) + fl(y cos)), heading += (float)angle; CPD_AUG_FLIP_X: columns 1 and 6 = -(v + 0); CPD_AUG_FLIP_Y:
+ * column 0 = -(v + 0), column 6 = -(v + (float)pi). Per class c < n_class HOST cls_floor [n_class] f32 (WBF_PRE_SCORES), cls_iou [n_class]
+ * f32 (WBF_IOUS) and cls_mode [n_class] i32: 0 or CPD_WBF_MAX for a fused class, CPD_TTA_MODE_NMS for a class that goes through NMS.
+ * Segment s = f * n_class + c (frame-major, classes in list order, empty ones included) is one workgroup: the candidate slots
+ * p = v * cap + row of frame f in ascending p; kept: row < counts[v * batch + f], label == c + 1, score >= cls_floor[c] (float32; NaN
+ * dropped); the kept slots by descending score, equal scores by ascending p (np.argsort(-scores, kind="stable")).
+ * Outputs, DEVICE, the segment's rows from the FIXED row s * n_views * cap: out_boxes [S * n_views * cap][7] after the backward
+ * transform, out_scores, out_src (the slot p); seg_start [S] = s * n_views * cap, seg_count [S], seg_thresh [S][2] = (cls_iou[c], 0),
+ * seg_mode [S] = cls_mode[c]: the arrays cpd_wbf_cluster reads; seg_count_wbf [S] = the count for a fused class and 0 for an NMS class,
+ * seg_count_nms [S] the reverse (cpd_nms_batch's counts with capacity n_views * cap). A segment of more than CPD_WBF_MAX_SEGMENT kept
+ * slots gets seg_count = seg_count_wbf = -1 (cpd_wbf_cluster's refusal), seg_count_nms = 0 and no rows.
+ * CPD_ERR_ARG: n_views outside 1 .. CPD_TTA_MAX_VIEWS, n_class > CPD_TTA_MAX_CLASSES, n_back[v] outside 0 .. CPD_AUG_MAX_OPS, an unknown
+ * op, a zero scale, S * n_views * cap >= 2^31, a null pointer.
+ *
+ * cpd_tta_collect_cpu: the same on the calling thread, HOST pointers throughout (the rules of csrc/tta_rules.h compiled for the host). */
+#define CPD_TTA_MAX_VIEWS 16
+#define CPD_TTA_MAX_CLASSES 16
+#define CPD_TTA_MODE_NMS (-1)
+int cpd_tta_views(const float *points, long long n_total, int c, const int64_t *frame_offsets, int batch, const int32_t *op_kind,
+                  const double *op_param, const int32_t *n_ops, int n_views, float *out, cpd_stream_t stream);
+int cpd_tta_collect(const float *boxes, const float *scores, const int64_t *labels, const int32_t *counts, int n_views, int batch, int cap,
+                    const int32_t *back_kind, const double *back_param, const int32_t *n_back, const float *cls_floor,
+                    const float *cls_iou, const int32_t *cls_mode, int n_class, float *out_boxes, float *out_scores, int32_t *out_src,
+                    int32_t *seg_start, int32_t *seg_count, int32_t *seg_count_wbf, int32_t *seg_count_nms, float *seg_thresh,
+                    int32_t *seg_mode, cpd_stream_t stream);
+int cpd_tta_collect_cpu(const float *boxes, const float *scores, const int64_t *labels, const int32_t *counts, int n_views, int batch,
+                        int cap, const int32_t *back_kind, const double *back_param, const int32_t *n_back, const float *cls_floor,
+                        const float *cls_iou, const int32_t *cls_mode, int n_class, float *out_boxes, float *out_scores,
+                        int32_t *out_src, int32_t *seg_start, int32_t *seg_count, int32_t *seg_count_wbf, int32_t *seg_count_nms,
+                        float *seg_thresh, int32_t *seg_mode);
+
 #ifdef __cplusplus
 }
 #endif
