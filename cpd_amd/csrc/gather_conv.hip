@@ -3065,44 +3065,6 @@ __global__ void __launch_bounds__(256) pack_weight_adjoint_kernel(const float *_
 
 typedef void (*gc_kernel_t)(GcParams);
 
-template <int MS, int NT>
-static gc_kernel_t pick_vec(bool vec) {
-    return vec ? gather_conv_kernel<MS, NT, true> : gather_conv_kernel<MS, NT, false>;
-}
-template <int MS>
-static gc_kernel_t pick_nt(int nt, bool vec) {
-    switch (nt) {
-        case 1: return pick_vec<MS, 1>(vec);
-        case 2: return pick_vec<MS, 2>(vec);
-        case 4: return pick_vec<MS, 4>(vec);
-        case 5: return pick_vec<MS, 5>(vec);
-        case 8: return pick_vec<MS, 8>(vec);
-    }
-    return nullptr;
-}
-static gc_kernel_t pick_h16(int ms, int nt) {           // 16-channel fp16-pair input: c_out = 16 or 32
-    if (ms == 1 && nt == 1) return gather_conv_kernel<1, 1, true, true>;
-    if (ms == 2 && nt == 1) return gather_conv_kernel<2, 1, true, true>;
-    if (ms == 1 && nt == 2) return gather_conv_kernel<1, 2, true, true>;
-    if (ms == 2 && nt == 2) return gather_conv_kernel<2, 2, true, true>;
-    return nullptr;
-}
-static gc_kernel_t pick(int ms, int nt, bool vec) {
-    switch (ms) {
-        case 1: return pick_nt<1>(nt, vec);
-        case 2: return pick_nt<2>(nt, vec);
-        case 4: return pick_nt<4>(nt, vec);
-    }
-    return nullptr;
-}
-static gc_kernel_t pick_tile(int bm, int bn) {
-    if (bm == 128 && bn == 128) return tile_conv_kernel<128, 128>;
-    if (bm == 64 && bn == 128) return tile_conv_kernel<64, 128>;
-    if (bm == 128 && bn == 64) return tile_conv_kernel<128, 64>;
-    if (bm == 64 && bn == 64) return tile_conv_kernel<64, 64>;
-    return nullptr;
-}
-
 // Wave tile choice (measured, tools/sweep_tiles.py on MI355X): per-wave efficiency grows with the
 // tile (B pieces reused across MS row sub-tiles, A pieces across NT column tiles) but fp32 MFMA
 // only needs one wave per SIMD, so what matters first is having >= ~4 wave tiles per SIMD (4096
@@ -3238,6 +3200,153 @@ static GcPlan plan(int n_out, int c_in, int c_out, int in_ld, const void *in, in
     if (const char *e = cpd_knob(tn, "CPD_GC_MS")) { int v = atoi(e); if (v == 1 || v == 2 || v == 4) pl.a = v; }
     if (const char *e = cpd_knob(tn, "CPD_GC_NT")) { int v = atoi(e); if ((v == 1 || v == 2 || v == 4 || v == 5 || v == 8) && ntot % v == 0) pl.b = v; }
     return pl;
+}
+
+// ---- which instantiation a launch runs, and what the launch log calls it ----
+// One row per conv instantiation the launchers run: the kernel, the label the launch log (cpd_launch_log_*) gives it -- what the
+// tests and the benchmark's per-kernel breakdown read -- and the launch geometry that belongs to the instantiation: threads per
+// workgroup and dynamic LDS bytes. A selector below returns a row (nullptr: no such kernel) and gc_launch() is the only place that
+// notes a label and launches, so the log names what ran. A label is its kernel's spelling without blanks, except where a row says
+// otherwise. (a, b): the keys a family's rows are found by -- GcPlan's (rows, columns) of a workgroup tile, (ms, nt) of a wave tile.
+struct GcKernel {
+    gc_kernel_t fn;
+    const char *label;
+    unsigned block, lds;
+};
+struct GcRow {
+    int a, b;
+    GcKernel k;
+};
+template <int N>
+static const GcKernel *gc_find(const GcRow (&rows)[N], int a, int b) {
+    for (const GcRow &r : rows)
+        if (r.a == a && r.b == b) return &r.k;
+    return nullptr;
+}
+
+// row-wave kernels <column tile, 16-row sub-tiles per wave>: 64 * MS rows per workgroup
+enum { RW_BF16, RW_F16, RW_F16S, RW_F16P, RW_F16E, RW_F16SE, RW_F16PE, RW_FAMILIES };
+#define GC_RW(F, BN, MS) {64 * MS, BN, {rowwave_conv_##F##_kernel<BN, MS>, "rowwave_conv_" #F "_kernel<" #BN "," #MS ">", 256, 0}}
+#define GC_RW_FAMILY(F) {GC_RW(F, 32, 1), GC_RW(F, 64, 1), GC_RW(F, 128, 1), GC_RW(F, 32, 2), GC_RW(F, 64, 2), GC_RW(F, 128, 2)}
+static const GcRow rowwave_rows[RW_FAMILIES][6] = {GC_RW_FAMILY(bf16), GC_RW_FAMILY(f16), GC_RW_FAMILY(f16s), GC_RW_FAMILY(f16p),
+                                                   GC_RW_FAMILY(f16e), GC_RW_FAMILY(f16se), GC_RW_FAMILY(f16pe)};
+#undef GC_RW_FAMILY
+#undef GC_RW
+// ... and their wide workgroups on pair rows: the label is <column tile, waves>, 32 rows and 64 threads per wave
+static_assert(CPD_RW_WIDE_WV(32) == 8 && CPD_RW_WIDE_WV(64) == 8 && CPD_RW_WIDE_WV(128) == 6, "the labels below spell the wave counts out");
+static const GcRow rowwave_wide_rows[] = {{256, 32, {rowwave_conv_f16pw_kernel<32>, "rowwave_conv_f16pw_kernel<32,8>", 512, 0}},
+                                          {256, 64, {rowwave_conv_f16pw_kernel<64>, "rowwave_conv_f16pw_kernel<64,8>", 512, 0}},
+                                          {192, 128, {rowwave_conv_f16pw_kernel<128>, "rowwave_conv_f16pw_kernel<128,6>", 384, 0}}};
+
+// split workgroup tiles <rows, columns>; LDS: one buffer of A and B stages per term (bf16x3: three, f16x2: two; twice that when double-buffered)
+enum { TILE_BF16, TILE_F16, TILE_F16S, TILE_FAMILIES };
+#define GC_TILE(F, BM, BN) {BM, BN, {tile_conv_##F##_kernel<BM, BN>, "tile_conv_" #F "_kernel<" #BM "," #BN ">", 256, 2 * (BM + BN) * 64}}
+static const GcRow split_tile_rows[TILE_FAMILIES][4] = {
+    {{64, 64, {tile_conv_bf16_kernel<64, 64, false>, "tile_conv_bf16_kernel<64,64>", 256, 3 * (64 + 64) * 64}},       // (64-row tiles: the small-problem variant,
+     {64, 128, {tile_conv_bf16_kernel<64, 128, false>, "tile_conv_bf16_kernel<64,128>", 256, 3 * (64 + 128) * 64}},   //  twice the workgroups)
+     {128, 64, {tile_conv_bf16_kernel<128, 64, false>, "tile_conv_bf16_kernel<128,64>", 256, 3 * (128 + 64) * 64}},
+     {128, 128, {tile_conv_bf16_kernel<128, 128, false>, "tile_conv_bf16_kernel<128,128>", 256, 3 * (128 + 128) * 64}}},
+    {GC_TILE(f16, 64, 64), GC_TILE(f16, 64, 128), GC_TILE(f16, 128, 64), GC_TILE(f16, 128, 128)},
+    {GC_TILE(f16s, 64, 64), GC_TILE(f16s, 64, 128), GC_TILE(f16s, 128, 64), GC_TILE(f16s, 128, 128)}};
+#undef GC_TILE
+static const GcKernel tile_bf16_db_row = {tile_conv_bf16_kernel<128, 128, true>, "tile_conv_bf16_kernel<128,128>", 256, 2 * 3 * (128 + 128) * 64};   // CPD_GC_BF16_DB
+// dense pair tile: its stages, or the epilogue's tile when that is larger
+static const GcKernel tile_f16p_row = {tile_conv_f16p_kernel, "tile_conv_f16p_kernel<128,128>", 256,
+                                       128 * 128 + 2 * 128 * 64 > 32 * 132 * 4 ? 128 * 128 + 2 * 128 * 64 : 32 * 132 * 4};
+
+// fp32 workgroup tiles <rows, columns>
+#define GC_TILE32(BM, BN) {BM, BN, {tile_conv_kernel<BM, BN>, "tile_conv_kernel<" #BM "," #BN ">", 256, 2 * (BM + BN) * 128}}
+static const GcRow tile_rows[] = {GC_TILE32(128, 128), GC_TILE32(64, 128), GC_TILE32(128, 64), GC_TILE32(64, 64)};
+#undef GC_TILE32
+
+// wave kernels <ms, nt, 16-byte A pieces>, four wave tiles per workgroup; h16: 16-channel fp16-pair input (c_out = 16 or 32)
+#define GC_WAVE(MS, NT, VEC) {MS, NT, {gather_conv_kernel<MS, NT, VEC>, "gather_conv_kernel<" #MS "," #NT "," #VEC ">", 256, 0}}
+#define GC_WAVE_MS(MS, VEC) GC_WAVE(MS, 1, VEC), GC_WAVE(MS, 2, VEC), GC_WAVE(MS, 4, VEC), GC_WAVE(MS, 5, VEC), GC_WAVE(MS, 8, VEC)
+static const GcRow wave_rows[2][15] = {{GC_WAVE_MS(1, false), GC_WAVE_MS(2, false), GC_WAVE_MS(4, false)},
+                                       {GC_WAVE_MS(1, true), GC_WAVE_MS(2, true), GC_WAVE_MS(4, true)}};
+#undef GC_WAVE_MS
+#undef GC_WAVE
+static const GcRow wave_h16_rows[] = {{1, 1, {gather_conv_kernel<1, 1, true, true>, "gather_conv_h16_kernel<1,1>", 256, 0}},
+                                      {2, 1, {gather_conv_kernel<2, 1, true, true>, "gather_conv_h16_kernel<2,1>", 256, 0}},
+                                      {1, 2, {gather_conv_kernel<1, 2, true, true>, "gather_conv_h16_kernel<1,2>", 256, 0}},
+                                      {2, 2, {gather_conv_kernel<2, 2, true, true>, "gather_conv_h16_kernel<2,2>", 256, 0}}};
+
+// The instantiation gather_conv_impl runs for a plan. scaled: an absmax block comes with the input (the pre-scaling f16s forms);
+// epi_lds: GcParams::epi_lds of a row-wave launch (the f16e / f16se / f16pe forms); in16: 16-channel pair rows.
+static const GcKernel *gather_kernel(const GcPlan &pl, bool scaled, bool in_pairs, bool epi_lds, bool in16) {
+    const bool f16 = pl.math == 2;
+    switch (pl.use_wg) {
+        case 3: {
+            if (pl.a > 128) return f16 && in_pairs ? gc_find(rowwave_wide_rows, pl.a, pl.b) : nullptr;
+            const int fam = !f16 ? RW_BF16
+                                 : (in_pairs ? (epi_lds ? RW_F16PE : RW_F16P) : (scaled ? (epi_lds ? RW_F16SE : RW_F16S) : (epi_lds ? RW_F16E : RW_F16)));
+            return gc_find(rowwave_rows[fam], pl.a, pl.b);
+        }
+        case 2: {
+            if (f16) return gc_find(split_tile_rows[scaled ? TILE_F16S : TILE_F16], pl.a, pl.b);
+            int db = 0;
+            if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_BF16_DB")) db = atoi(e);
+            return db && pl.a == 128 && pl.b == 128 ? &tile_bf16_db_row : gc_find(split_tile_rows[TILE_BF16], pl.a, pl.b);
+        }
+        case 1: return gc_find(tile_rows, pl.a, pl.b);
+    }
+    return in16 ? gc_find(wave_h16_rows, pl.a, pl.b) : gc_find(wave_rows[pl.vec != 0], pl.a, pl.b);
+}
+
+// window kernels <columns, rows> (the rows keyed (rows, columns) like the others); the label always spells the rows out
+constexpr unsigned window_bf16_lds(int bn) { return 3 * ((128 + 16) * 64 + bn * 64); }
+constexpr unsigned window_f16_lds(int bn, int bm) {      // window image + weights (two weight buffers on the 64- / 128-column tiles)
+    return 2 * (bm + 16) * 64 + (bn >= 64 ? 2 : 1) * 2 * bn * 64;
+}
+// (round 6, measured and NOT kept: padding the pair kernels' LDS so that only TWO 128 x 128 workgroups fit a CU -- room for a sparse
+// kernel of the other batch in flight on the same CU, matrix pipe and vector-memory pipe side by side -- 1219.9 / 1217.7 frames/s
+// without, 1191.9 / 1176.6 with 26 KB of padding, 1034.1 / 1021.5 with 40 KB: gpurun_out r06_winpad)
+constexpr unsigned window_f16p_lds(int bn, int bm) {
+    const unsigned win = (bm + 8) * 128, wts = bn >= 64 ? 2 * 2 * bn * 64 : 2 * bn * 64, tile = 64 * (bn + 4) * 4;
+    return win + wts > tile ? win + wts : tile;
+}
+constexpr unsigned window_f16p16_lds(int bm) { return (bm + 8) * 128 + 2 * 3 * 2 * 4 * 16 * 16; }
+#define GC_WIN(F, BN, BM, LDS) {BM, BN, {window_conv_##F##_kernel<BN, BM>, "window_conv_" #F "_kernel<" #BN "," #BM ">", 256, LDS}}
+#define GC_WIN_F16(F) {GC_WIN(F, 128, 128, window_f16_lds(128, 128)), GC_WIN(F, 64, 128, window_f16_lds(64, 128)), GC_WIN(F, 16, 128, window_f16_lds(16, 128)), \
+                       GC_WIN(F, 64, 256, window_f16_lds(64, 256)), GC_WIN(F, 16, 256, window_f16_lds(16, 256))}
+static const GcRow window_bf16_rows[] = {{128, 128, {window_conv_bf16_kernel<128>, "window_conv_bf16_kernel<128,128>", 256, window_bf16_lds(128)}},
+                                         {128, 64, {window_conv_bf16_kernel<64>, "window_conv_bf16_kernel<64,128>", 256, window_bf16_lds(64)}},
+                                         {128, 16, {window_conv_bf16_kernel<16>, "window_conv_bf16_kernel<16,128>", 256, window_bf16_lds(16)}}};
+static const GcRow window_f16_rows[2][5] = {GC_WIN_F16(f16), GC_WIN_F16(f16s)};      // [pre-scaled input]
+static const GcRow window_f16p_rows[] = {GC_WIN(f16p, 128, 128, window_f16p_lds(128, 128)), GC_WIN(f16p, 64, 256, window_f16p_lds(64, 256)),
+                                         GC_WIN(f16p, 64, 128, window_f16p_lds(64, 128)),      // (4 ... 7-frame batches)
+                                         GC_WIN(f16p, 16, 256, window_f16p_lds(16, 256))};     // (CPD_GC_P16_GROUPED = 0)
+// the 16-column head tile: stage groups of three taps, next group's rows and weights a whole group ahead (window_conv_pairs16_body)
+static const GcRow window_f16p16_rows[] = {{128, 16, {window_conv_f16p16_kernel<128>, "window_conv_f16p_kernel<16,128>", 256, window_f16p16_lds(128)}},
+                                           {256, 16, {window_conv_f16p16_kernel<256>, "window_conv_f16p_kernel<16,256>", 256, window_f16p16_lds(256)}}};
+#undef GC_WIN_F16
+#undef GC_WIN
+
+// The instantiation conv3x3_rows_impl runs for a (bm x bn) tile
+static const GcKernel *window_kernel(int math, bool scaled, bool in_pairs, int bm, int bn) {
+    if (in_pairs && bn == 16) {
+        int grouped = 1;
+        if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_P16_GROUPED")) grouped = atoi(e);
+        if (bm == 128 || grouped) return gc_find(window_f16p16_rows, bm, bn);
+    }
+    if (in_pairs) return gc_find(window_f16p_rows, bm, bn);
+    return math == 2 ? gc_find(window_f16_rows[scaled], bm, bn) : gc_find(window_bf16_rows, bm, bn);
+}
+
+// staged row-wave kernels <columns, taps per weight stage, rows per tile>, keyed (rows per tile, columns); two threads per row
+static const GcRow rowplan_rows[] = {{128, 32, {rowplan_conv_f16p_kernel<32, 3>, "rowplan_conv_f16p_kernel<32>", 256, 0}},
+                                     {128, 64, {rowplan_conv_f16p_kernel<64, 3>, "rowplan_conv_f16p_kernel<64>", 256, 0}},
+                                     {128, 128, {rowplan_conv_f16p_kernel<128, 3>, "rowplan_conv_f16p_kernel<128>", 256, 0}},
+                                     {256, 32, {rowplan_conv_f16p_kernel<32, 3, 256>, "rowplan_conv_f16p_kernel<32,256>", 512, 0}},
+                                     {256, 64, {rowplan_conv_f16p_kernel<64, 3, 256>, "rowplan_conv_f16p_kernel<64,256>", 512, 0}},
+                                     {256, 128, {rowplan_conv_f16p_kernel<128, 1, 256>, "rowplan_conv_f16p_kernel<128,256>", 512, 0}}};
+static const GcKernel rowplan_tb9_row = {rowplan_conv_f16p_kernel<32, 9>, "rowplan_conv_f16p_kernel<32>", 256, 0};
+
+// The instantiation cpd_gather_conv_planned runs
+static const GcKernel *rowplan_kernel(int tile_rows, int c_out) {
+    int tb32 = 3;             // 32 columns: the three dx taps of one dy per weight stage (12 KB, 3 workgroups per CU: 443 us) or all nine (36 KB, 2: 559 us)
+    if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_PLANNED_TB32")) tb32 = atoi(e);
+    return tile_rows == 128 && c_out == 32 && tb32 != 3 ? &rowplan_tb9_row : gc_find(rowplan_rows, tile_rows, c_out);
 }
 
 }  // namespace
@@ -3523,6 +3632,14 @@ extern "C" int cpd_gather_conv_tile(int n_out, int c_in, int c_out, int in_ld, i
     *a = pl.a; *b = pl.b; *vec = pl.vec;
     return CPD_OK;
 }
+extern "C" const char *cpd_gather_conv_label(int n_out, int c_in, int c_out, int in_ld, int kv, int flags, int scaled) {
+    if (n_out <= 0 || c_in <= 0 || c_out <= 0) return nullptr;
+    GcPlan pl = plan(n_out, c_in, c_out, in_ld, nullptr, flags);
+    if (pl.use_wg == 3 && kv > CPD_RW_TAPS) pl = plan(n_out, c_in, c_out, in_ld, nullptr, flags | CPD_GC_DENSE);     // as gather_conv_impl does
+    const bool in_pairs = (flags & CPD_GC_IN_PAIRS) != 0;
+    const GcKernel *k = gather_kernel(pl, scaled != 0, in_pairs, false, in_pairs && c_in == 16);
+    return k ? k->label : nullptr;
+}
 
 // Tap split of a SMALL row-wave launch (one frame, the train step): a workgroup walks its row tile's (tap, 32-channel block) stages
 // one after the other -- 108 of them at 128 channels, ~0.9 us each when a CU holds one or two workgroups -- so a layer with fewer
@@ -3563,6 +3680,14 @@ static int rowwave_finish(const GcParams &p, hipStream_t hs) {      // after a r
     return cpd_check_launch();
 }
 
+// The one launch of a conv kernel: the row's label into the launch log, its kernel with its own block size and LDS bytes, then the
+// second half of a tap split (only row-wave and split-tile launches have p.split > 1)
+static int gc_launch(const GcKernel &k, dim3 grid, hipStream_t hs, const GcParams &p) {
+    cpd_launch_log_note(k.label);
+    hipLaunchKernelGGL(k.fn, grid, dim3(k.block), k.lds, hs, p);
+    return rowwave_finish(p, hs);
+}
+
 static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, const float *packed_w, const int32_t *nbr,
                             const uint32_t *tapmask, int kv, int n_out, int c_out, const float *scale, const float *shift,
                             const float *residual, int res_ld, int relu, float *out, int out_ld,
@@ -3597,10 +3722,7 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
         p.wb = packed_f16_ptr(packed_w, kv, c_in, c_out);
         p.dsc = packed_dsc_ptr(packed_w, kv, c_in, c_out);
         p.n_rb = (n_out + 127) / 128; p.n_cb = c_out / 128; p.items = p.n_rb * p.n_cb;
-        cpd_launch_log_note("tile_conv_f16p_kernel<128,128>");
-        hipLaunchKernelGGL(tile_conv_f16p_kernel, dim3(p.items), dim3(256), 128 * 128 + 2 * 128 * 64 > 32 * 132 * 4 ? 128 * 128 + 2 * 128 * 64 : 32 * 132 * 4,
-                           cpd_s(stream), p);
-        return cpd_check_launch();
+        return gc_launch(tile_f16p_row, dim3(p.items), cpd_s(stream), p);
     }
     if ((flags & CPD_GC_IN_PAIRS) && !in16 &&
         (!(flags & CPD_GC_F16X2) || (flags & CPD_GC_DENSE) || c_in % 32 || c_out % 32 || in_ld % 4 || in_absmax || kv > CPD_RW_TAPS ||
@@ -3663,139 +3785,22 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
     if (pl.use_wg == 2)      // the 128 x 128 split tile kernels' LDS epilogue: 16-byte pieces when the operands allow (element accesses otherwise)
         p.epi_lds = out_ld % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!out_col_group || out_col_group % 4 == 0) &&
                     (!residual || (res_ld % 4 == 0 && (((uintptr_t)residual) & 15) == 0));
-    const dim3 grid(p.items, p.split), block(pl.use_wg == 3 && pl.a > 128 ? pl.a * 2 : 256);
-    {   // launch log (cpd_launch_log_*): the instantiation this call runs
-        char nm[96];
-        const bool e = pl.use_wg == 3 && p.epi_lds;      // (the LDS-epilogue instantiations of the row-wave kernels: f16e / f16se / f16pe)
-        const char *sc = (pl.math == 2 && in_absmax) ? (e ? "f16se" : "f16s") : (pl.math == 2 ? (p.in_pairs ? (e ? "f16pe" : "f16p") : (e ? "f16e" : "f16")) : "bf16");
-        if (pl.use_wg == 3 && pl.a > 128) snprintf(nm, sizeof nm, "rowwave_conv_f16pw_kernel<%d,%d>", pl.b, pl.a / 32);
-        else if (pl.use_wg == 3) snprintf(nm, sizeof nm, "rowwave_conv_%s_kernel<%d,%d>", sc, pl.b, pl.a / 64);
-        else if (pl.use_wg == 2) snprintf(nm, sizeof nm, "tile_conv_%s_kernel<%d,%d>", sc, pl.a, pl.b);
-        else if (pl.use_wg == 1) snprintf(nm, sizeof nm, "tile_conv_kernel<%d,%d>", pl.a, pl.b);
-        else if (in16) snprintf(nm, sizeof nm, "gather_conv_h16_kernel<%d,%d>", pl.a, pl.b);
-        else snprintf(nm, sizeof nm, "gather_conv_kernel<%d,%d,%s>", pl.a, pl.b, pl.vec ? "true" : "false");
-        cpd_launch_log_note(nm);
-    }
-#define CPD_LAUNCH(K, LDS) hipLaunchKernelGGL((K), grid, block, (LDS), hs, p)
-#define CPD_RW_EPI_LAUNCH(NAME)                                                   \
-    do {                                                                          \
-        if (pl.a == 64) {                                                         \
-            if (pl.b == 32) CPD_LAUNCH((NAME<32, 1>), 0);                         \
-            else if (pl.b == 64) CPD_LAUNCH((NAME<64, 1>), 0);                    \
-            else CPD_LAUNCH((NAME<128, 1>), 0);                                   \
-        } else if (pl.b == 32) CPD_LAUNCH((NAME<32, 2>), 0);                      \
-        else if (pl.b == 64) CPD_LAUNCH((NAME<64, 2>), 0);                        \
-        else CPD_LAUNCH((NAME<128, 2>), 0);                                       \
-        return rowwave_finish(p, hs);                                             \
-    } while (0)
-    if (pl.use_wg == 3 && pl.math == 2 && p.epi_lds && !p.in_pairs) {
-        if (in_absmax) CPD_RW_EPI_LAUNCH(rowwave_conv_f16se_kernel);
-        else CPD_RW_EPI_LAUNCH(rowwave_conv_f16e_kernel);
-    }
-    if (pl.use_wg == 3 && pl.math == 2 && in_absmax) {
-        if (pl.a == 64) {
-            if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16s_kernel<32, 1>), 0);
-            else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16s_kernel<64, 1>), 0);
-            else CPD_LAUNCH((rowwave_conv_f16s_kernel<128, 1>), 0);
-        } else if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16s_kernel<32, 2>), 0);
-        else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16s_kernel<64, 2>), 0);
-        else CPD_LAUNCH((rowwave_conv_f16s_kernel<128, 2>), 0);
-        return rowwave_finish(p, hs);
-    }
-    if (pl.use_wg == 3 && pl.math == 2 && p.in_pairs && p.epi_lds) {
-        if (pl.a == 64) {
-            if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16pe_kernel<32, 1>), 0);
-            else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16pe_kernel<64, 1>), 0);
-            else CPD_LAUNCH((rowwave_conv_f16pe_kernel<128, 1>), 0);
-        } else if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16pe_kernel<32, 2>), 0);
-        else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16pe_kernel<64, 2>), 0);
-        else CPD_LAUNCH((rowwave_conv_f16pe_kernel<128, 2>), 0);
-        return rowwave_finish(p, hs);
-    }
-    if (pl.use_wg == 3 && pl.math == 2 && p.in_pairs) {
-        if (pl.a > 128) {
-            if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16pw_kernel<32>), 0);
-            else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16pw_kernel<64>), 0);
-            else CPD_LAUNCH((rowwave_conv_f16pw_kernel<128>), 0);
-        } else if (pl.a == 64) {
-            if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16p_kernel<32, 1>), 0);
-            else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16p_kernel<64, 1>), 0);
-            else CPD_LAUNCH((rowwave_conv_f16p_kernel<128, 1>), 0);
-        } else if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16p_kernel<32, 2>), 0);
-        else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16p_kernel<64, 2>), 0);
-        else CPD_LAUNCH((rowwave_conv_f16p_kernel<128, 2>), 0);
-        return rowwave_finish(p, hs);
-    }
-    if (pl.use_wg == 3 && pl.math == 2) {
-        if (pl.a == 64) {
-            if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16_kernel<32, 1>), 0);
-            else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16_kernel<64, 1>), 0);
-            else CPD_LAUNCH((rowwave_conv_f16_kernel<128, 1>), 0);
-        } else if (pl.b == 32) CPD_LAUNCH((rowwave_conv_f16_kernel<32, 2>), 0);
-        else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_f16_kernel<64, 2>), 0);
-        else CPD_LAUNCH((rowwave_conv_f16_kernel<128, 2>), 0);
-        return rowwave_finish(p, hs);
-    }
-    if (pl.use_wg == 3) {
-        if (pl.a == 64) {
-            if (pl.b == 32) CPD_LAUNCH((rowwave_conv_bf16_kernel<32, 1>), 0);
-            else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_bf16_kernel<64, 1>), 0);
-            else CPD_LAUNCH((rowwave_conv_bf16_kernel<128, 1>), 0);
-        } else if (pl.b == 32) CPD_LAUNCH((rowwave_conv_bf16_kernel<32, 2>), 0);
-        else if (pl.b == 64) CPD_LAUNCH((rowwave_conv_bf16_kernel<64, 2>), 0);
-        else CPD_LAUNCH((rowwave_conv_bf16_kernel<128, 2>), 0);
-        return rowwave_finish(p, hs);
-    }
-    if (pl.use_wg == 2 && pl.math == 2) {
-        const size_t lds = 2 * (size_t)(pl.a + pl.b) * 64;
-        if (in_absmax) {
-            if (pl.a == 64 && pl.b == 128) CPD_LAUNCH((tile_conv_f16s_kernel<64, 128>), lds);
-            else if (pl.a == 64) CPD_LAUNCH((tile_conv_f16s_kernel<64, 64>), lds);
-            else if (pl.b == 64) CPD_LAUNCH((tile_conv_f16s_kernel<128, 64>), lds);
-            else CPD_LAUNCH((tile_conv_f16s_kernel<128, 128>), lds);
-            return rowwave_finish(p, hs);
-        }
-        if (pl.a == 64 && pl.b == 128) CPD_LAUNCH((tile_conv_f16_kernel<64, 128>), lds);
-        else if (pl.a == 64) CPD_LAUNCH((tile_conv_f16_kernel<64, 64>), lds);
-        else if (pl.b == 64) CPD_LAUNCH((tile_conv_f16_kernel<128, 64>), lds);
-        else CPD_LAUNCH((tile_conv_f16_kernel<128, 128>), lds);
-        return rowwave_finish(p, hs);
-    }
-    if (pl.use_wg == 2) {
-        int db = 0;
-        if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_BF16_DB")) db = atoi(e);
-        if (pl.b == 64) db = 0;
-        if (pl.a == 64) {                                   // small-problem variant: 64-row tiles double the workgroup count
-            const size_t lds64 = 3 * (size_t)(64 + pl.b) * 64;
-            if (pl.b == 128) CPD_LAUNCH((tile_conv_bf16_kernel<64, 128, false>), lds64);
-            else CPD_LAUNCH((tile_conv_bf16_kernel<64, 64, false>), lds64);
-            return rowwave_finish(p, hs);
-        }
-        const size_t lds = (db ? 2 : 1) * 3 * (size_t)(pl.a + pl.b) * 64;
+    const GcKernel *k = gather_kernel(pl, in_absmax != nullptr, p.in_pairs, p.epi_lds, in16);
+    if (!k) return CPD_ERR_UNSUPPORTED;
+    if (pl.use_wg == 2 || pl.use_wg == 3) {
         static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&tile_conv_bf16_kernel<128, 128, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 3 * (128 + 128) * 64);
+        if (k == &tile_bf16_db_row && !attr_set) {        // two buffers of three terms: more than the 64 KB a launch gets unasked
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, k->lds);
             attr_set = true;
         }
-        if (pl.b == 64) CPD_LAUNCH((tile_conv_bf16_kernel<128, 64, false>), lds);
-        else if (db) CPD_LAUNCH((tile_conv_bf16_kernel<128, 128, true>), lds);
-        else CPD_LAUNCH((tile_conv_bf16_kernel<128, 128, false>), lds);
-        return rowwave_finish(p, hs);
+        return gc_launch(*k, dim3(p.items, p.split), hs, p);
     }
-#undef CPD_LAUNCH
     if (pl.use_wg) {
-        gc_kernel_t k = pick_tile(pl.a, pl.b);
-        if (!k) return CPD_ERR_UNSUPPORTED;
         p.n_rb = (n_out + pl.a - 1) / pl.a;
         p.n_cb = c_out / pl.b;
         p.items = p.n_rb * p.n_cb;
-        size_t lds = 2 * (size_t)(pl.a + pl.b) * 128;
-        hipLaunchKernelGGL(k, dim3(p.items), dim3(256), lds, cpd_s(stream), p);
-        return cpd_check_launch();
+        return gc_launch(*k, dim3(p.items), hs, p);
     }
-    gc_kernel_t k = in16 ? pick_h16(pl.a, pl.b) : pick(pl.a, pl.b, pl.vec != 0);
-    if (!k) return CPD_ERR_UNSUPPORTED;
     if (in16) {
         p.wb = packed_h16_ptr(packed_w, kv, c_in, c_out);
         p.dsc = reinterpret_cast<const float *>(p.wb) + packed_h16_image_floats(kv, c_in, c_out);
@@ -3815,9 +3820,7 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
     p.n_rb = (n_out + 16 * pl.a - 1) / (16 * pl.a);
     p.n_cb = p.ntot / pl.b;
     p.items = p.n_rb * p.n_cb;
-    int blocks = (p.items + 3) / 4;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, cpd_s(stream), p);
-    return cpd_check_launch();
+    return gc_launch(*k, dim3((p.items + 3) / 4), hs, p);
 }
 
 // ---- dense 3x3 / stride 1 / pad 1 over pixel rows, no rulebook (window_conv_bf16_kernel) ----
@@ -3911,67 +3914,11 @@ static int conv3x3_rows_impl(const float *in, int in_ld, int frames, int h, int 
         // (window_conv_f16p_kernel). The batch sizes that take the 128 x 128 / 256 x 64 / 256 x 16 tiles; no residual, no pre-scaling
         const bool pin = (flags & CPD_GC_IN_PAIRS) != 0, pout = (flags & CPD_GC_OUT_PAIRS) != 0;
         if (!pin || (flags & CPD_GC_RES_PAIRS) || residual || in_absmax || math != 2 || (bn >= 64 && !p.epi_lds)) return CPD_ERR_UNSUPPORTED;
-        if (!((bn == 128 && bm == 128) || (bn == 64 && (bm == 256 || bm == 128)) || (bn == 16 && (bm == 256 || bm == 128)))) return CPD_ERR_UNSUPPORTED;
         if (pout != (bn >= 64)) return CPD_ERR_UNSUPPORTED;
         p.in_pairs = 1; p.out_pairs = pout ? 1 : 0;
-        char nm[96];
-        snprintf(nm, sizeof nm, "window_conv_f16p_kernel<%d,%d>", bn, bm);
-        cpd_launch_log_note(nm);
-        const size_t win = (size_t)(bm + 8) * 128, tile = (size_t)64 * (bn + 4) * 4;
-        const size_t wts = bn >= 64 ? 2 * 2 * (size_t)bn * 64 : 2 * (size_t)bn * 64;
-        // (round 6, measured and NOT kept: padding this launch's LDS so that only TWO 128 x 128 workgroups fit a CU -- room for a sparse
-        // kernel of the other batch in flight on the same CU, matrix pipe and vector-memory pipe side by side -- 1219.9 / 1217.7 frames/s
-        // without, 1191.9 / 1176.6 with 26 KB of padding, 1034.1 / 1021.5 with 40 KB: gpurun_out r06_winpad)
-        const size_t ldsp = win + wts > tile ? win + wts : tile;
-        if (bn == 128) hipLaunchKernelGGL((window_conv_f16p_kernel<128, 128>), dim3(p.items), dim3(256), ldsp, cpd_s(stream), p);
-        else if (bn == 64 && bm == 256) hipLaunchKernelGGL((window_conv_f16p_kernel<64, 256>), dim3(p.items), dim3(256), ldsp, cpd_s(stream), p);
-        else if (bn == 64) hipLaunchKernelGGL((window_conv_f16p_kernel<64, 128>), dim3(p.items), dim3(256), ldsp, cpd_s(stream), p);      // (4 ... 7-frame batches)
-        else if (bm == 128) hipLaunchKernelGGL((window_conv_f16p16_kernel<128>), dim3(p.items), dim3(256), win + 2 * 3 * 2 * 4 * 16 * 16, cpd_s(stream), p);
-        else {
-            // the 16-column head tile: stage groups of three taps, next group's rows and weights a whole group ahead (window_conv_pairs16_body)
-            int grouped = 1;
-            if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_P16_GROUPED")) grouped = atoi(e);
-            if (grouped) hipLaunchKernelGGL((window_conv_f16p16_kernel<256>), dim3(p.items), dim3(256), win + 2 * 3 * 2 * 4 * 16 * 16, cpd_s(stream), p);
-            else hipLaunchKernelGGL((window_conv_f16p_kernel<16, 256>), dim3(p.items), dim3(256), ldsp, cpd_s(stream), p);
-        }
-        return cpd_check_launch();
     }
-    {
-        char nm[96];
-        snprintf(nm, sizeof nm, "window_conv_%s_kernel<%d,%d>", math == 2 ? (in_absmax ? "f16s" : "f16") : "bf16", bn, bm);
-        cpd_launch_log_note(nm);
-    }
-    const size_t lds = (math == 2 ? 2 : 3) * ((size_t)(128 + 16) * 64 + (size_t)bn * 64);
-    if (math == 2 && bm == 256 && in_absmax) {
-        const size_t ldsa = 2 * (size_t)(256 + 16) * 64;
-        if (bn == 64) hipLaunchKernelGGL((window_conv_f16s_kernel<64, 256>), dim3(p.items), dim3(256), ldsa + 2 * 2 * 64 * 64, cpd_s(stream), p);
-        else hipLaunchKernelGGL((window_conv_f16s_kernel<16, 256>), dim3(p.items), dim3(256), ldsa + 2 * 16 * 64, cpd_s(stream), p);
-        return cpd_check_launch();
-    }
-    if (math == 2 && in_absmax) {
-        const size_t lds2 = 2 * (size_t)(128 + 16) * 64 + 2 * 2 * (size_t)bn * 64;
-        if (bn == 128) hipLaunchKernelGGL((window_conv_f16s_kernel<128>), dim3(p.items), dim3(256), lds2, cpd_s(stream), p);
-        else if (bn == 64) hipLaunchKernelGGL((window_conv_f16s_kernel<64>), dim3(p.items), dim3(256), lds2, cpd_s(stream), p);
-        else hipLaunchKernelGGL((window_conv_f16s_kernel<16>), dim3(p.items), dim3(256), lds, cpd_s(stream), p);
-        return cpd_check_launch();
-    }
-    if (math == 2 && bm == 256) {
-        const size_t ldsa = 2 * (size_t)(256 + 16) * 64;
-        if (bn == 64) hipLaunchKernelGGL((window_conv_f16_kernel<64, 256>), dim3(p.items), dim3(256), ldsa + 2 * 2 * 64 * 64, cpd_s(stream), p);
-        else hipLaunchKernelGGL((window_conv_f16_kernel<16, 256>), dim3(p.items), dim3(256), ldsa + 2 * 16 * 64, cpd_s(stream), p);
-        return cpd_check_launch();
-    }
-    if (math == 2) {
-        const size_t lds2 = 2 * (size_t)(128 + 16) * 64 + 2 * 2 * (size_t)bn * 64;    // window image + two weight buffers
-        if (bn == 128) hipLaunchKernelGGL((window_conv_f16_kernel<128>), dim3(p.items), dim3(256), lds2, cpd_s(stream), p);
-        else if (bn == 64) hipLaunchKernelGGL((window_conv_f16_kernel<64>), dim3(p.items), dim3(256), lds2, cpd_s(stream), p);
-        else hipLaunchKernelGGL((window_conv_f16_kernel<16>), dim3(p.items), dim3(256), lds, cpd_s(stream), p);
-        return cpd_check_launch();
-    }
-    if (bn == 128) hipLaunchKernelGGL((window_conv_bf16_kernel<128>), dim3(p.items), dim3(256), lds, cpd_s(stream), p);
-    else if (bn == 64) hipLaunchKernelGGL((window_conv_bf16_kernel<64>), dim3(p.items), dim3(256), lds, cpd_s(stream), p);
-    else hipLaunchKernelGGL((window_conv_bf16_kernel<16>), dim3(p.items), dim3(256), lds, cpd_s(stream), p);
-    return cpd_check_launch();
+    const GcKernel *k = window_kernel(math, in_absmax != nullptr, p.in_pairs, bm, bn);      // (pair rows: the 128 x 128, 256 / 128 x 64 and 256 / 128 x 16 tiles)
+    return k ? gc_launch(*k, dim3(p.items), cpd_s(stream), p) : CPD_ERR_UNSUPPORTED;
 }
 
 extern "C" int cpd_gather_conv(const float *in, int in_ld, int n_in, int c_in, const float *packed_w, const int32_t *nbr,
@@ -4036,23 +3983,8 @@ extern "C" int cpd_gather_conv_planned(const float *in, int in_ld, int n_in, int
     p.dsc = packed_dsc_ptr(packed_w, kv, c_in, c_out);
     p.plan_slots = plan_slots; p.plan_ulist = plan_ulist; p.plan_count = plan_count;
     p.n_rb = (n_out + 127) / 128; p.n_cb = 1; p.items = p.n_rb;
-    char nm[64];
-    snprintf(nm, sizeof nm, tile_rows == 256 ? "rowplan_conv_f16p_kernel<%d,256>" : "rowplan_conv_f16p_kernel<%d>", c_out);
-    cpd_launch_log_note(nm);
-    const dim3 grid(p.items), block(256);
-    hipStream_t hs = cpd_s(stream);
-    int tb32 = 3;             // 32 columns: the three dx taps of one dy per weight stage (12 KB, 3 workgroups per CU: 443 us) or all nine (36 KB, 2: 559 us)
-    if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_PLANNED_TB32")) tb32 = atoi(e);
-    if (tile_rows == 256) {
-        const dim3 grid2((n_out + 255) / 256), block2(512);
-        if (c_out == 32) hipLaunchKernelGGL((rowplan_conv_f16p_kernel<32, 3, 256>), grid2, block2, 0, hs, p);
-        else if (c_out == 64) hipLaunchKernelGGL((rowplan_conv_f16p_kernel<64, 3, 256>), grid2, block2, 0, hs, p);
-        else hipLaunchKernelGGL((rowplan_conv_f16p_kernel<128, 1, 256>), grid2, block2, 0, hs, p);
-    } else if (c_out == 32 && tb32 == 3) hipLaunchKernelGGL((rowplan_conv_f16p_kernel<32, 3>), grid, block, 0, hs, p);
-    else if (c_out == 32) hipLaunchKernelGGL((rowplan_conv_f16p_kernel<32, 9>), grid, block, 0, hs, p);
-    else if (c_out == 64) hipLaunchKernelGGL((rowplan_conv_f16p_kernel<64, 3>), grid, block, 0, hs, p);
-    else hipLaunchKernelGGL((rowplan_conv_f16p_kernel<128, 3>), grid, block, 0, hs, p);
-    return cpd_check_launch();
+    const GcKernel *k = rowplan_kernel(tile_rows, c_out);
+    return k ? gc_launch(*k, dim3((n_out + tile_rows - 1) / tile_rows), cpd_s(stream), p) : CPD_ERR_UNSUPPORTED;
 }
 extern "C" size_t cpd_gather_conv_split_bytes(int n_out, int c_in, int c_out, int in_ld, int kv, int flags) {
     if (n_out <= 0 || c_in <= 0 || c_out <= 0 || kv <= 0) return 0;

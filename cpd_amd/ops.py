@@ -959,44 +959,24 @@ def boxes_iou_bev_cpu(a, b):
     return out
 
 
-RW_TAPS = 28                 # CPD_RW_TAPS of csrc/gather_conv.hip: the most taps a row-wave launch takes
-
-
 def gather_conv_tile(n_out, c_in, c_out, in_ld, dense=False, bf16x3=False, nbr=None, math=None, scaled=False, in_pairs=False, kv=None):
     """Name of the kernel instantiation gather_conv will run for this problem (`nbr`: the table it would be given; `scaled`: an
     `in_absmax` block comes with the input -- the split-fp16 kernels then run as their pre-scaling `f16s` instantiations; `kv`: the
-    tap count, when known -- a kernel with more taps than the row-wave kernels keep is planned as a dense layer, as the launcher does)."""
-    if nbr is not None and getattr(nbr, "plan", None) is not None and not scaled and lib().cpd_gather_conv_planned_supported(
-            int(nbr.shape[1]), int(n_out), int(c_in), int(c_out), int(in_ld), int(nbr.shape[0]),
-            _gc_flags(dense, bf16x3, math) | (16 if in_pairs else 0) | 32):      # (the staged kernel writes pair rows)
-        return "rowplan_conv_f16p_kernel<%d%s>" % (c_out, ",256" if nbr.plan[3] == 256 else "")
-    name = _gather_conv_tile(n_out, c_in, c_out, in_ld, dense, bf16x3, nbr, math, in_pairs)
-    if kv is not None and kv > RW_TAPS and name.startswith("rowwave_conv_"):
-        name = _gather_conv_tile(n_out, c_in, c_out, in_ld, True, bf16x3, nbr, math, in_pairs)
-    return name.replace("_f16_kernel", "_f16s_kernel") if scaled else name
-
-
-def _gather_conv_tile(n_out, c_in, c_out, in_ld, dense=False, bf16x3=False, nbr=None, math=None, in_pairs=False):
-    image = getattr(nbr, "image", None)
+    tap count, when known -- a kernel with more taps than the row-wave kernels keep is planned as a dense layer, as the launcher does).
+    The staged and window kernels are tried in gather_conv's own order; every other name is the launcher's (cpd_gather_conv_label)."""
     flags = _gc_flags(dense, bf16x3, math) | (16 if in_pairs else 0)
+    if nbr is not None and getattr(nbr, "plan", None) is not None and not scaled and lib().cpd_gather_conv_planned_supported(
+            int(nbr.shape[1]), int(n_out), int(c_in), int(c_out), int(in_ld), int(nbr.shape[0]), flags | 32):      # (the staged kernel writes pair rows)
+        return "rowplan_conv_f16p_kernel<%d%s>" % (c_out, ",256" if nbr.plan[3] == 256 else "")
+    image = getattr(nbr, "image", None)
     if image is not None and n_out == image[0] * image[1] * image[2] and in_ld % 4 == 0 and lib().cpd_conv3x3_rows_supported(
             image[0], image[1], image[2], int(c_in), int(c_out), flags):
         bm, bn = ctypes.c_int(0), ctypes.c_int(0)
         check(lib().cpd_conv3x3_rows_tile(image[0], image[1], image[2], int(c_in), int(c_out), flags, ctypes.byref(bm), ctypes.byref(bn)),
               "cpd_conv3x3_rows_tile")
-        return "window_conv_%s_kernel<%s>" % ("f16" if flags & 4 else "bf16", "%d" % bn.value if bm.value == 128 else "%d,%d" % (bn.value, bm.value))
-    wg, a, b, vec = (ctypes.c_int(0) for _ in range(4))
-    check(lib().cpd_gather_conv_tile(int(n_out), int(c_in), int(c_out), int(in_ld), flags,
-                                     ctypes.byref(wg), ctypes.byref(a), ctypes.byref(b), ctypes.byref(vec)),
-          "cpd_gather_conv_tile")
-    if wg.value == 13 and a.value > 128:
-        return "rowwave_conv_f16pw_kernel<%d,%d>" % (b.value, a.value // 32)            # wide workgroups: <column tile, waves>
-    if wg.value in (3, 13):
-        return "rowwave_conv_%s_kernel<%d,%d>" % (("f16p" if flags & 16 else "f16") if wg.value == 13 else "bf16", b.value, a.value // 64)   # <column tile, row sub-tiles per wave>
-    if wg.value in (2, 12):
-        return "tile_conv_%s_kernel<%d,%d>" % ("f16" if wg.value == 12 else "bf16", a.value, b.value)
-    if wg.value:
-        return "tile_conv_kernel<%d,%d>" % (a.value, b.value)
-    if in_pairs and c_in == 16:
-        return "gather_conv_h16_kernel<%d,%d>" % (a.value, b.value)                   # 16-channel pair rows: the K = 16 MFMA form
-    return "gather_conv_kernel<%d,%d,%s>" % (a.value, b.value, "true" if vec.value else "false")
+        return "window_conv_%s_kernel<%s>" % (("f16s" if scaled else "f16") if flags & 4 else "bf16",
+                                              "%d" % bn.value if bm.value == 128 else "%d,%d" % (bn.value, bm.value))
+    name = lib().cpd_gather_conv_label(int(n_out), int(c_in), int(c_out), int(in_ld), int(kv or 0), flags, int(bool(scaled)))
+    if name is None:
+        raise _lib.CpdHipError("cpd_gather_conv_label: no kernel for n_out=%d c_in=%d c_out=%d flags=%d" % (n_out, c_in, c_out, flags))
+    return name.decode()

@@ -297,6 +297,11 @@ int cpd_gather_conv_planned(const float *in, int in_ld, int n_in, int c_in, cons
  * gather_conv_kernel<a,b,vec> ((16a) x (16b) wave tile; vec = 16-byte A pieces). HOST only.  */
 int cpd_gather_conv_tile(int n_out, int c_in, int c_out, int in_ld, int flags, int *wg, int *a,
                          int *b, int *vec);
+/* ... and the launch-log label (cpd_launch_log_*) of that instantiation, from the launcher's own table -- for a problem described
+ * without pointers: operands taken as 16-byte aligned, the row-wave kernels' plain (not LDS-epilogue) forms. kv: the tap count
+ * (0: unknown; more taps than a row-wave launch keeps are planned as a dense layer, as the launcher does); scaled: an in_absmax
+ * block comes with the input (the f16s forms). A static string; NULL when no kernel takes the problem. HOST only. */
+const char *cpd_gather_conv_label(int n_out, int c_in, int c_out, int in_ld, int kv, int flags, int scaled);
 
 /* SparseConvTensor.dense() + view(N, C*D, H, W) (height_compression.py:136-138).
  *   nchw: out (B, C*D, H, W), channel = c*D + z   -- the reference layout
