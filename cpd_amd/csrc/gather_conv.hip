@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "absmax.h"
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -83,6 +84,35 @@ struct GcParams {
     const int32_t *plan_count;    // [tiles][4]: list lengths of the three groups
 };
 
+// ---- the fp16-pair row layout (GcParams::in_pairs / out_pairs / res_pairs above), as byte offsets inside a row ----
+// 32-channel form: block b = channels 32 b .. 32 b + 31 is 128 bytes, 64 B of high terms then 64 B of low terms.
+// 16-channel form (a 16-channel row, *_pairs == 2): k-group k = channels 4 k .. 4 k + 3 is 16 bytes, [hi 4 | lo 4].
+constexpr int PAIR32_LO = 64, PAIR16_LO = 8;         // from a channel's high term to its low term
+__host__ __device__ __forceinline__ constexpr int pair32_off(int col) { return ((col >> 5) << 7) + ((col & 31) << 1); }       // high term of channel col
+__host__ __device__ __forceinline__ constexpr int pair32_unit_off(int unit) { return ((unit >> 2) << 7) + ((unit & 3) << 4); }   // high terms of channels 8 unit .. 8 unit + 7: one 16-byte piece
+__host__ __device__ __forceinline__ constexpr int pair16_off(int col) { return ((col >> 2) << 4) + ((col & 3) << 1); }
+// the numbers ops.rows_to_pairs and the tests' pair_round assume
+static_assert(pair32_off(0) == 0 && pair32_off(31) == 62 && pair32_off(32) == 128, "32 high terms, 32 low terms, next block");
+static_assert(pair32_unit_off(5) == 128 + 16 && pair32_unit_off(5) == pair32_off(40), "a unit is 8 channels");
+static_assert(pair16_off(5) == 16 + 2, "[hi 4 | lo 4] per k-group");
+// The split x = h + l of SplitF16x2 (below): h = rne(x), l = rne(x - h); h + l is exact in fp32
+__device__ __forceinline__ void split_pair(float v, _Float16 &h, _Float16 &l) {
+    h = (_Float16)v;
+    l = (_Float16)(v - (float)h);
+}
+__device__ __forceinline__ void split_pair(const f32x4 &v, f16x4 &h, f16x4 &l) {
+    h = __builtin_convertvector(v, f16x4);
+    l = __builtin_convertvector(v - __builtin_convertvector(h, f32x4), f16x4);
+}
+__device__ __forceinline__ void split_pair(const float (&v)[8], f16x8 &h, f16x8 &l) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        h[q] = (_Float16)v[q];
+        l[q] = (_Float16)(v[q] - (float)h[q]);
+    }
+}
+__device__ __forceinline__ float join_pair(_Float16 h, _Float16 l) { return (float)h + (float)l; }
+
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     // Bijective "contiguous chunk per XCD" remap (workgroup b runs on XCD b % 8; speed only).
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
@@ -111,29 +141,22 @@ __device__ __forceinline__ f32x4 zero_if(f32x4 a, bool z) {
     return a;
 }
 
-// Shared epilogue. C/D layout of 16x16x4: col = lane & 15, row = 4*(lane >> 4) + i.
-// Power-of-two pre-scale of the input for the fp16 split: s = 2^(14 - floor(log2 max|in|)), inv = 1 / s (both exact)
-__device__ __forceinline__ void in_pow2_scale(const uint32_t *absmax, float &s, float &inv) {
-    s = 1.f; inv = 1.f;
-    if (absmax) {
-        // the maximum is kept as CPD_ABSMAX_SLOTS partial maxima, one per 128-byte line (same-line atomics serialise)
-        uint32_t m = absmax[(threadIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE];
+// Column set-up of the LDS epilogues: for the NT columns col_of(nt) a lane holds accumulators of, sc = scale * dsc * in_inv (the
+// order the shared epilogue multiplies in; in_inv = 1 where the input is not pre-scaled) and sh = shift. No bound checks: those
+// epilogues' tiles are whole, where the shared epilogue below bounds its columns (and keeps its own form)
+template <int NT, class F>
+__device__ __forceinline__ void col_affine(const GcParams &p, F col_of, float in_inv, float (&sc)[NT], float (&sh)[NT]) {
 #pragma unroll
-        for (int o = CPD_ABSMAX_SLOTS / 2; o > 0; o >>= 1) {
-            const uint32_t t = (uint32_t)__shfl_xor((int)m, o);
-            m = t > m ? t : m;
-        }
-        m = (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
-        const int e = (int)((m >> 23) & 0xffu);                // biased exponent of max |in|
-        if (e != 0 && e != 255) {                              // zero / denormal / inf / nan maximum: left alone
-            int se = 268 - e;                                  // 127 + 14 - (e - 127)
-            se = se < 1 ? 1 : (se > 253 ? 253 : se);
-            s = __uint_as_float((uint32_t)se << 23);
-            inv = __uint_as_float((uint32_t)(254 - se) << 23);
-        }
+    for (int nt = 0; nt < NT; ++nt) {
+        const int col = col_of(nt);
+        sc[nt] = p.scale ? p.scale[col] : 1.f;
+        if (p.dsc) sc[nt] *= p.dsc[col];
+        sc[nt] *= in_inv;
+        sh[nt] = p.shift ? p.shift[col] : 0.f;
     }
 }
 
+// Shared epilogue. C/D layout of 16x16x4: col = lane & 15, row = 4*(lane >> 4) + i.
 // PAIRS: the instantiation honours p.out_pairs / p.res_pairs (the sparse kernels; elsewhere the flags are refused by the launcher)
 template <int MS, int NT, bool PAIRS = false>
 __device__ __forceinline__ void epilogue(const GcParams &p, f32x4 (&acc)[MS][NT], int row0, int col0, int r, int g, float acc_scale = 1.f) {
@@ -171,12 +194,13 @@ __device__ __forceinline__ void epilogue(const GcParams &p, f32x4 (&acc)[MS][NT]
                     const int nt = c0 + nc;
                     int col = col0 + nt * 16 + r;
                     col = col < p.c_out ? col : p.c_out - 1;
+                    // (pair16_off / pair32_off / join_pair spelled out: with them gather_conv_kernel<4,5>'s VGPR count moves 424 -> 388, <1,4>'s 116 -> 120)
                     if (PAIRS && p.res_pairs == 2) {  // 16-channel pair rows: k-group (col >> 2) = [hi 4 | lo 4]
                         const char *rp = reinterpret_cast<const char *>(p.residual + (size_t)rowc * p.res_ld) + ((col >> 2) << 4) + ((col & 3) << 1);
-                        resv[i][nc] = (float)*reinterpret_cast<const _Float16 *>(rp) + (float)*reinterpret_cast<const _Float16 *>(rp + 8);
+                        resv[i][nc] = (float)*reinterpret_cast<const _Float16 *>(rp) + (float)*reinterpret_cast<const _Float16 *>(rp + PAIR16_LO);
                     } else if (PAIRS && p.res_pairs) {       // h + l is exact in fp32
                         const char *rp = reinterpret_cast<const char *>(p.residual + (size_t)rowc * p.res_ld) + ((col >> 5) << 7) + ((col & 31) << 1);
-                        resv[i][nc] = (float)*reinterpret_cast<const _Float16 *>(rp) + (float)*reinterpret_cast<const _Float16 *>(rp + 64);
+                        resv[i][nc] = (float)*reinterpret_cast<const _Float16 *>(rp) + (float)*reinterpret_cast<const _Float16 *>(rp + PAIR32_LO);
                     } else {
                         resv[i][nc] = p.residual[(size_t)rowc * p.res_ld + col];
                     }
@@ -200,8 +224,7 @@ __device__ __forceinline__ void epilogue(const GcParams &p, f32x4 (&acc)[MS][NT]
                 v = v * sc[nt] + sh[nt];
                 if (p.residual) v += resv[i][nc];
                 if (p.relu) v = v > 0.f ? v : 0.f;
-                const uint32_t vb = __float_as_uint(v) & 0x7fffffffu;
-                vmax = vb > vmax ? vb : vmax;
+                absmax_note(vmax, v);
                 if (p.col_group) {
                     if (grp[nt] != grp_have) {                 // one map entry per (row, group): a column tile rarely spans two
                         grp_have = grp[nt];
@@ -211,15 +234,15 @@ __device__ __forceinline__ void epilogue(const GcParams &p, f32x4 (&acc)[MS][NT]
                 } else if (PAIRS && p.out_pairs) {
                     // fp16-pair row: lanes r, r ^ 1 (columns col, col ^ 1; same row) trade their (h, l): the even lane stores the two
                     // high terms, the odd lane the two low terms -- one 4-byte store per lane, as for an fp32 row
-                    const _Float16 h = (_Float16)v;
-                    const _Float16 l = (_Float16)(v - (float)h);
+                    _Float16 h, l;
+                    split_pair(v, h, l);
                     const uint32_t mine = (uint32_t)__builtin_bit_cast(unsigned short, h) | ((uint32_t)__builtin_bit_cast(unsigned short, l) << 16);
                     const uint32_t theirs = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
                     const bool odd = (r & 1) != 0;
                     const uint32_t word = odd ? ((theirs >> 16) | (mine & 0xffff0000u)) : ((mine & 0xffffu) | (theirs << 16));
                     char *op = reinterpret_cast<char *>(p.out + orow * p.out_ld);
-                    if (p.out_pairs == 2) op += ((col >> 2) << 4) + (odd ? 8 : 0) + ((col & 2) << 1);          // 16-channel pair rows
-                    else op += ((col >> 5) << 7) + (odd ? 64 : 0) + ((col & 30) << 1);
+                    if (p.out_pairs == 2) op += pair16_off(col & ~1) + (odd ? PAIR16_LO : 0);          // 16-channel pair rows
+                    else op += pair32_off(col & ~1) + (odd ? PAIR32_LO : 0);
                     *reinterpret_cast<uint32_t *>(op) = word;
                 } else {
                     p.out[orow * p.out_ld + col] = v;
@@ -228,19 +251,7 @@ __device__ __forceinline__ void epilogue(const GcParams &p, f32x4 (&acc)[MS][NT]
         }
         }
     }
-    if (p.out_absmax) {
-        // one (rarely issued) atomic per wave: the slot is read past the L1 first and raised only when this wave holds a larger
-        // value -- after the first workgroups almost nobody does. Slots sit on CPD_ABSMAX_SLOTS different 128-byte lines.
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-            vmax = t > vmax ? t : vmax;
-        }
-        if ((threadIdx.x & 63) == 0) {
-            uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-            if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-        }
-    }
+    absmax_raise(p.out_absmax, vmax);
 }
 
 // ================================== wave kernel ==============================================
@@ -469,13 +480,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(H16 &&
             constexpr int LD = 16 * NT + 4;
             float *const stile = reinterpret_cast<float *>(&s_idx[wave][0][0]);
             float sc[NT], sh[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int col = col0 + 16 * nt + r;
-                sc[nt] = p.scale ? p.scale[col] : 1.f;
-                if (p.dsc) sc[nt] *= p.dsc[col];
-                sh[nt] = p.shift ? p.shift[col] : 0.f;
-            }
+            col_affine<NT>(p, [&](int nt) { return col0 + 16 * nt + r; }, 1.f, sc, sh);
             uint32_t vmax = 0;
             const int urow = lane >> 2, piece = lane & 3;
 #pragma unroll
@@ -490,61 +495,50 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(H16 &&
                 const int rowc = row < p.n_out ? row : p.n_out - 1;
                 if constexpr (NT == 1) {                     // [hi 4 | lo 4] of k-group `piece`
                     f32x4 v = *reinterpret_cast<const f32x4 *>(stile + urow * LD + 4 * piece);
+                    const int off = pair16_off(col0 + 4 * piece);
                     if (p.residual) {
-                        const f16x8 x = *reinterpret_cast<const f16x8 *>(reinterpret_cast<const char *>(p.residual + (size_t)rowc * p.res_ld) + (((col0 >> 2) + piece) << 4));
+                        const f16x8 x = *reinterpret_cast<const f16x8 *>(reinterpret_cast<const char *>(p.residual + (size_t)rowc * p.res_ld) + off);
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] += (float)x[q] + (float)x[4 + q];
+                        for (int q = 0; q < 4; ++q) v[q] += join_pair(x[q], x[4 + q]);
                     }
-                    f16x8 o;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         if (p.relu) v[q] = v[q] > 0.f ? v[q] : 0.f;
-                        const uint32_t vb = __float_as_uint(v[q]) & 0x7fffffffu;
-                        vmax = (row < p.n_out && vb > vmax) ? vb : vmax;
-                        o[q] = (_Float16)v[q];
-                        o[4 + q] = (_Float16)(v[q] - (float)o[q]);
+                        absmax_note(vmax, v[q], row < p.n_out);
                     }
-                    if (row < p.n_out) *reinterpret_cast<f16x8 *>(reinterpret_cast<char *>(p.out + (size_t)row * p.out_ld) + (((col0 >> 2) + piece) << 4)) = o;
+                    f16x4 h, l;
+                    split_pair(v, h, l);
+                    if (row < p.n_out)
+                        *reinterpret_cast<f16x8 *>(reinterpret_cast<char *>(p.out + (size_t)row * p.out_ld) + off) = __builtin_shufflevector(h, l, 0, 1, 2, 3, 4, 5, 6, 7);
                 } else {                                     // 8 channels of a 32-channel block: high terms, low terms 64 bytes on
                     const f32x4 v0 = *reinterpret_cast<const f32x4 *>(stile + urow * LD + 8 * piece);
                     const f32x4 v1 = *reinterpret_cast<const f32x4 *>(stile + urow * LD + 8 * piece + 4);
-                    const int unit = (col0 >> 3) + piece;
-                    const int off = ((unit >> 2) << 7) + ((unit & 3) << 4);
+                    const int off = pair32_unit_off((col0 >> 3) + piece);
                     f16x8 rh = {}, rl = {};
                     if (p.residual) {
                         const char *rp = reinterpret_cast<const char *>(p.residual + (size_t)rowc * p.res_ld) + off;
                         rh = *reinterpret_cast<const f16x8 *>(rp);
-                        rl = *reinterpret_cast<const f16x8 *>(rp + 64);
+                        rl = *reinterpret_cast<const f16x8 *>(rp + PAIR32_LO);
                     }
-                    f16x8 h, l;
+                    float t[8];
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         float v = q < 4 ? v0[q] : v1[q - 4];
-                        if (p.residual) v += (float)rh[q] + (float)rl[q];
+                        if (p.residual) v += join_pair(rh[q], rl[q]);
                         if (p.relu) v = v > 0.f ? v : 0.f;
-                        const uint32_t vb = __float_as_uint(v) & 0x7fffffffu;
-                        vmax = (row < p.n_out && vb > vmax) ? vb : vmax;
-                        h[q] = (_Float16)v;
-                        l[q] = (_Float16)(v - (float)h[q]);
+                        absmax_note(vmax, v, row < p.n_out);
+                        t[q] = v;
                     }
+                    f16x8 h, l;
+                    split_pair(t, h, l);
                     if (row < p.n_out) {
                         char *op = reinterpret_cast<char *>(p.out + (size_t)row * p.out_ld) + off;
                         *reinterpret_cast<f16x8 *>(op) = h;
-                        *reinterpret_cast<f16x8 *>(op + 64) = l;
+                        *reinterpret_cast<f16x8 *>(op + PAIR32_LO) = l;
                     }
                 }
             }
-            if (p.out_absmax) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-                    vmax = t > vmax ? t : vmax;
-                }
-                if (lane == 0) {
-                    uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-                    if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-                }
-            }
+            absmax_raise(p.out_absmax, vmax);
             return;
         }
     }
@@ -720,9 +714,7 @@ struct SplitF16x2 {
     typedef f16x8 frag;
     typedef f16x4 half;
     static __device__ __forceinline__ void split(const f32x4 &x, half (&p)[NP]) {
-        p[0] = __builtin_convertvector(x, f16x4);
-        const f32x4 r1 = x - __builtin_convertvector(p[0], f32x4);
-        p[1] = __builtin_convertvector(r1, f16x4);
+        split_pair(x, p[0], p[1]);
     }
     static __device__ __forceinline__ f32x4 mma(const frag (&a)[NP], const frag (&b)[NP], f32x4 c) {
         if (!(CPD_GC_ABLATE & 2048)) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);   // 2048: two of three products (timing only)
@@ -898,7 +890,7 @@ __device__ __forceinline__ void tile_conv_split_body(const GcParams &p) {
         float *const stile = reinterpret_cast<float *>(smem);
         float sc[NT], sh[NT];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
+        for (int nt = 0; nt < NT; ++nt) {       // (col_affine() spelled out: with it tile_conv_bf16_kernel<128,128,true>'s SGPR count moves 81 -> 82)
             const int col = col0 + wc * (BN / 2) + nt * 16 + r;
             sc[nt] = p.scale ? p.scale[col] : 1.f;
             if (p.dsc) sc[nt] *= p.dsc[col];
@@ -936,8 +928,7 @@ __device__ __forceinline__ void tile_conv_split_body(const GcParams &p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if (p.relu) v[q] = v[q] > 0.f ? v[q] : 0.f;
-                    const uint32_t vb = __float_as_uint(v[q]) & 0x7fffffffu;
-                    vmax = vb > vmax ? vb : vmax;
+                    absmax_note(vmax, v[q]);
                 }
                 if (p.epi_lds) {
                     float *op;
@@ -957,17 +948,7 @@ __device__ __forceinline__ void tile_conv_split_body(const GcParams &p) {
                 }
             }
         }
-        if (p.out_absmax) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-                vmax = t > vmax ? t : vmax;
-            }
-            if (lane == 0) {
-                uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-                if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-            }
-        }
+        absmax_raise(p.out_absmax, vmax);
     } else {
         epilogue<MS, NT>(p, acc, row0 + wr * (BM / 2), col0 + wc * (BN / 2), r, g, in_inv);
     }
@@ -1268,14 +1249,7 @@ __device__ __forceinline__ void window_conv_split_body(const GcParams &p) {
         static_assert(WM == 64, "a pass is one wave row");
         float *const stile = reinterpret_cast<float *>(smem);
         float sc[NT], sh[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col = col0 + wc * WN + nt * 16 + r;
-            sc[nt] = p.scale ? p.scale[col] : 1.f;
-            if (p.dsc) sc[nt] *= p.dsc[col];
-            sc[nt] *= in_inv;
-            sh[nt] = p.shift ? p.shift[col] : 0.f;
-        }
+        col_affine<NT>(p, [&](int nt) { return col0 + wc * WN + nt * 16 + r; }, in_inv, sc, sh);
         uint32_t vmax = 0;
         const int c4 = tid % C4, urow = tid / C4;
 #pragma unroll 1
@@ -1305,24 +1279,13 @@ __device__ __forceinline__ void window_conv_split_body(const GcParams &p) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if (p.relu) v[q] = v[q] > 0.f ? v[q] : 0.f;
-                    const uint32_t vb = __float_as_uint(v[q]) & 0x7fffffffu;
-                    vmax = vb > vmax ? vb : vmax;
+                    absmax_note(vmax, v[q]);
                 }
                 if (p.epi_lds) *reinterpret_cast<f32x4 *>(op) = v;
                 else { op[0] = v[0]; op[1] = v[1]; op[2] = v[2]; op[3] = v[3]; }
             }
         }
-        if (p.out_absmax) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-                vmax = t > vmax ? t : vmax;
-            }
-            if (lane == 0) {
-                uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-                if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-            }
-        }
+        absmax_raise(p.out_absmax, vmax);
     } else {
         epilogue<MS, NT>(p, acc, row0 + wr * WM, col0 + wc * (BN / WC), r, g, in_inv);
     }
@@ -1559,16 +1522,10 @@ __device__ __forceinline__ void window_conv_pairs_body(const GcParams &p) {
         static_assert(WM == 64, "a pass is one wave row");
         float *const stile = reinterpret_cast<float *>(smem);
         float sc[NT], sh[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col = col0 + wc * WN + nt * 16 + r;
-            sc[nt] = p.scale ? p.scale[col] : 1.f;
-            if (p.dsc) sc[nt] *= p.dsc[col];
-            sh[nt] = p.shift ? p.shift[col] : 0.f;
-        }
+        col_affine<NT>(p, [&](int nt) { return col0 + wc * WN + nt * 16 + r; }, 1.f, sc, sh);
         uint32_t vmax = 0;
         const int c8 = tid % C8, urow = tid / C8;
-        const int pair_off = (((col0 >> 3) + c8) >> 2 << 7) + ((((col0 >> 3) + c8) & 3) << 4);
+        const int pair_off = pair32_unit_off((col0 >> 3) + c8);
 #pragma unroll 1
         for (int pass = 0; pass < WR; ++pass) {
             __syncthreads();
@@ -1588,32 +1545,22 @@ __device__ __forceinline__ void window_conv_pairs_body(const GcParams &p) {
                 if (row >= p.n_out) continue;
                 const f32x4 v0 = *reinterpret_cast<const f32x4 *>(stile + lrow * LD + 8 * c8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4 *>(stile + lrow * LD + 8 * c8 + 4);
-                f16x8 h, l;
+                float t[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     float v = q < 4 ? v0[q] : v1[q - 4];
                     if (p.relu) v = v > 0.f ? v : 0.f;
-                    const uint32_t vb = __float_as_uint(v) & 0x7fffffffu;
-                    vmax = vb > vmax ? vb : vmax;
-                    h[q] = (_Float16)v;
-                    l[q] = (_Float16)(v - (float)h[q]);
+                    absmax_note(vmax, v);
+                    t[q] = v;
                 }
+                f16x8 h, l;
+                split_pair(t, h, l);
                 char *const orow = reinterpret_cast<char *>(p.out + (size_t)row * p.out_ld);
                 *reinterpret_cast<f16x8 *>(orow + pair_off) = h;
-                *reinterpret_cast<f16x8 *>(orow + pair_off + 64) = l;
+                *reinterpret_cast<f16x8 *>(orow + pair_off + PAIR32_LO) = l;
             }
         }
-        if (p.out_absmax) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint32_t t2 = (uint32_t)__shfl_xor((int)vmax, o);
-                vmax = t2 > vmax ? t2 : vmax;
-            }
-            if (lane == 0) {
-                uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-                if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-            }
-        }
+        absmax_raise(p.out_absmax, vmax);
     } else {
         epilogue<MS, NT>(p, acc, row0 + wr * WM, col0 + wc * (BN / WC), r, g, 1.f);       // the 16-column head tile: fp32 rows out (decode reads them)
     }
@@ -1913,18 +1860,12 @@ tile_conv_f16p_kernel(GcParams p) {
         constexpr int LD = BN + 4, C8 = BN / 8, RPI = 256 / C8, UNITS = 32 / RPI;
         float *const stile = reinterpret_cast<float *>(smem);
         float sc[NT], sh[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col = col0 + wc * (BN / 2) + nt * 16 + r;
-            sc[nt] = p.scale ? p.scale[col] : 1.f;
-            if (p.dsc) sc[nt] *= p.dsc[col];
-            sh[nt] = p.shift ? p.shift[col] : 0.f;
-        }
+        col_affine<NT>(p, [&](int nt) { return col0 + wc * (BN / 2) + nt * 16 + r; }, 1.f, sc, sh);
         uint32_t vmax = 0;
         const int c8 = tid % C8, urow = tid / C8;
         const int col = col0 + 8 * c8;
         const int grp = p.col_group ? col / p.col_group : 0, cloc = col - grp * p.col_group;
-        const int pair_off = ((cloc >> 5) << 7) + (((cloc >> 3) & 3) << 4);
+        const int pair_off = pair32_unit_off(cloc >> 3);
 #pragma unroll
         for (int pass = 0; pass < 4; ++pass) {       // (unrolled: the accumulator indices must be constants)
             __syncthreads();
@@ -1945,35 +1886,25 @@ tile_conv_f16p_kernel(GcParams p) {
                 if (row >= p.n_out) continue;
                 const f32x4 v0 = *reinterpret_cast<const f32x4 *>(stile + lrow * LD + 8 * c8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4 *>(stile + lrow * LD + 8 * c8 + 4);
-                f16x8 h, l;
+                float t[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     float v = q < 4 ? v0[q] : v1[q - 4];
                     if (p.relu) v = v > 0.f ? v : 0.f;
-                    const uint32_t vb = __float_as_uint(v) & 0x7fffffffu;
-                    vmax = vb > vmax ? vb : vmax;
-                    h[q] = (_Float16)v;
-                    l[q] = (_Float16)(v - (float)h[q]);
+                    absmax_note(vmax, v);
+                    t[q] = v;
                 }
+                f16x8 h, l;
+                split_pair(t, h, l);
                 size_t orow_i;
                 if (p.col_group) orow_i = (size_t)p.out_row_map[(size_t)grp * p.n_out + row];
                 else orow_i = p.out_row_map ? (size_t)p.out_row_map[row] : (size_t)row;
                 char *const orow = reinterpret_cast<char *>(p.out + orow_i * p.out_ld);
                 *reinterpret_cast<f16x8 *>(orow + pair_off) = h;
-                *reinterpret_cast<f16x8 *>(orow + pair_off + 64) = l;
+                *reinterpret_cast<f16x8 *>(orow + pair_off + PAIR32_LO) = l;
             }
         }
-        if (p.out_absmax) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint32_t t2 = (uint32_t)__shfl_xor((int)vmax, o);
-                vmax = t2 > vmax ? t2 : vmax;
-            }
-            if (lane == 0) {
-                uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-                if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-            }
-        }
+        absmax_raise(p.out_absmax, vmax);
     }
 }
 
@@ -2339,21 +2270,14 @@ __device__ __forceinline__ void rowwave_conv_split_body(const GcParams &p, char 
                                                      // 64-column kernel sits at its register budget (95 of 96) and spilled an accumulator otherwise
         const int cg = ln % UPR, urow = ln / UPR;
         float sc[NT], sh[NT];                        // scale / shift in fragment coordinates, as the accumulators leave the registers
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col = col0 + 16 * nt + rc;
-            sc[nt] = p.scale ? p.scale[col] : 1.f;
-            if (p.dsc) sc[nt] *= p.dsc[col];
-            sc[nt] *= in_inv;
-            sh[nt] = p.shift ? p.shift[col] : 0.f;
-        }
+        col_affine<NT>(p, [&](int nt) { return col0 + 16 * nt + rc; }, in_inv, sc, sh);
         uint32_t vmax = 0;
         // a unit's two 16-byte pieces in a row of `out` / `residual`: pair rows -- the high terms of its 8 channels, the low terms 64 bytes
         // on --, fp32 rows -- channels 0-3 and 4-7
-        const int pair_off = (((col0 >> 3) + cg) >> 2 << 7) + ((((col0 >> 3) + cg) & 3) << 4);
+        const int pair_off = pair32_unit_off((col0 >> 3) + cg);
         const int f32_off = (col0 + 8 * cg) * 4;
         const int res_off = OP ? pair_off : f32_off;
-        constexpr int res_2nd = OP ? 64 : 16;
+        constexpr int res_2nd = OP ? PAIR32_LO : 16;
 #pragma unroll
         for (int pass = 0; pass < 16 * MS / EPI_R; ++pass) {
             __syncthreads();                         // every wave is done with the last stage's LDS (or, wave by wave, the previous pass's tile)
@@ -2392,29 +2316,24 @@ __device__ __forceinline__ void rowwave_conv_split_body(const GcParams &p, char 
                 for (int q = 0; q < 8; ++q) {
                     float v = q < 4 ? v0[q] : v1[q - 4];
                     if (p.residual) {
-                        if constexpr (OP) v += (float)__builtin_bit_cast(f16x8, ra[k % UC])[q] + (float)__builtin_bit_cast(f16x8, rb[k % UC])[q];   // h + l is exact in fp32
+                        if constexpr (OP) v += join_pair(__builtin_bit_cast(f16x8, ra[k % UC])[q], __builtin_bit_cast(f16x8, rb[k % UC])[q]);   // h + l is exact in fp32
                         else v += q < 4 ? ra[k % UC][q] : rb[k % UC][q - 4];
                     }
                     if (p.relu) v = v > 0.f ? v : 0.f;
                     t[q] = v;
-                    const uint32_t vb = __float_as_uint(v) & 0x7fffffffu;
-                    vmax = (row < p.n_out && vb > vmax) ? vb : vmax;
+                    absmax_note(vmax, v, row < p.n_out);
                 }
                 if (row < p.n_out) {
                     char *const orow = reinterpret_cast<char *>(p.out + (size_t)row * p.out_ld);
                     if constexpr (OP) {
                         f16x8 h, l;
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            h[q] = (_Float16)t[q];
-                            l[q] = (_Float16)(t[q] - (float)h[q]);
-                        }
+                        split_pair(t, h, l);
                         if (CPD_RW_NT & 1) {
                             __builtin_nontemporal_store(h, reinterpret_cast<f16x8 *>(orow + pair_off));
-                            __builtin_nontemporal_store(l, reinterpret_cast<f16x8 *>(orow + pair_off + 64));
+                            __builtin_nontemporal_store(l, reinterpret_cast<f16x8 *>(orow + pair_off + PAIR32_LO));
                         } else {
                             *reinterpret_cast<f16x8 *>(orow + pair_off) = h;
-                            *reinterpret_cast<f16x8 *>(orow + pair_off + 64) = l;
+                            *reinterpret_cast<f16x8 *>(orow + pair_off + PAIR32_LO) = l;
                         }
                     } else {
                         *reinterpret_cast<f32x4 *>(orow + f32_off) = f32x4{t[0], t[1], t[2], t[3]};
@@ -2423,17 +2342,7 @@ __device__ __forceinline__ void rowwave_conv_split_body(const GcParams &p, char 
                 }
             }
         }
-        if (p.out_absmax) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-                vmax = t > vmax ? t : vmax;
-            }
-            if (lane == 0) {
-                uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-                if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-            }
-        }
+        absmax_raise(p.out_absmax, vmax);
     }
 }
 
@@ -2454,12 +2363,12 @@ __global__ void __launch_bounds__(256) split_finish_kernel(GcParams p) {
         if (p.dsc) sc *= *reinterpret_cast<const f32x4 *>(p.dsc + col);
         sc *= in_inv;
         const f32x4 sh = p.shift ? *reinterpret_cast<const f32x4 *>(p.shift + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const int pair_off = ((col >> 5) << 7) + ((col & 31) << 1);      // byte offset of the four high terms inside a pair row
+        const int pair_off = pair32_off(col);      // byte offset of the four high terms inside a pair row
         f32x4 res = {0.f, 0.f, 0.f, 0.f};
         if (p.residual) {
             if (p.res_pairs) {
                 const char *rp = reinterpret_cast<const char *>(p.residual + (size_t)row * p.res_ld) + pair_off;
-                const f16x4 h = *reinterpret_cast<const f16x4 *>(rp), l = *reinterpret_cast<const f16x4 *>(rp + 64);
+                const f16x4 h = *reinterpret_cast<const f16x4 *>(rp), l = *reinterpret_cast<const f16x4 *>(rp + PAIR32_LO);
                 res = __builtin_convertvector(h, f32x4) + __builtin_convertvector(l, f32x4);
             } else {
                 res = *reinterpret_cast<const f32x4 *>(p.residual + (size_t)row * p.res_ld + col);
@@ -2471,30 +2380,19 @@ __global__ void __launch_bounds__(256) split_finish_kernel(GcParams p) {
             if (p.residual) t += res[k];
             if (p.relu) t = t > 0.f ? t : 0.f;
             v[k] = t;
-            const uint32_t vb = __float_as_uint(t) & 0x7fffffffu;
-            vmax = vb > vmax ? vb : vmax;
+            absmax_note(vmax, t);
         }
         if (p.out_pairs) {
-            const f16x4 h = __builtin_convertvector(v, f16x4);
-            const f16x4 l = __builtin_convertvector(v - __builtin_convertvector(h, f32x4), f16x4);
+            f16x4 h, l;
+            split_pair(v, h, l);
             char *op = reinterpret_cast<char *>(p.out + orow * p.out_ld) + pair_off;
             *reinterpret_cast<f16x4 *>(op) = h;
-            *reinterpret_cast<f16x4 *>(op + 64) = l;
+            *reinterpret_cast<f16x4 *>(op + PAIR32_LO) = l;
         } else {
             *reinterpret_cast<f32x4 *>(p.out + orow * p.out_ld + col) = v;
         }
     }
-    if (p.out_absmax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-            vmax = t > vmax ? t : vmax;
-        }
-        if ((threadIdx.x & 63) == 0) {
-            uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-            if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-        }
-    }
+    absmax_raise(p.out_absmax, vmax);
 }
 
 // (bf16x3, BN = 128, MS = 2 sits at the 3-waves-per-SIMD budget)
@@ -2745,9 +2643,10 @@ __device__ __forceinline__ void rowplan_conv_body(const GcParams &p, char *const
             const int k = k0 + kc;
             const int row = tile * ROWS + pass * EPI_ROWS + urow0 + k * UR;
             const int rowc = row < p.n_out ? row : p.n_out - 1;
+            // (pair32_unit_off(cg) spelled out, here and at the store below: with it the VGPR counts of <128,1,256> (176) and <64,3,128> (220) move)
             const char *rp = reinterpret_cast<const char *>(p.residual + (size_t)rowc * p.res_ld) + ((cg >> 2) << 7) + ((cg & 3) << 4);
             rh[kc] = *reinterpret_cast<const f16x8 *>(rp);
-            rl[kc] = *reinterpret_cast<const f16x8 *>(rp + 64);
+            rl[kc] = *reinterpret_cast<const f16x8 *>(rp + PAIR32_LO);
         }
         res_issued = true;
     };
@@ -2827,7 +2726,7 @@ __device__ __forceinline__ void rowplan_conv_body(const GcParams &p, char *const
     float *const stile = reinterpret_cast<float *>(smem);
     float sc[8], sh[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
+    for (int q = 0; q < 8; ++q) {               // (a thread's 8 adjacent columns; col_affine() moves rowplan_conv_f16p_kernel<64,3,128>'s VGPR count 220 -> 212)
         const int col = 8 * cg + q;
         sc[q] = p.scale ? p.scale[col] : 1.f;
         if (p.dsc) sc[q] *= p.dsc[col];
@@ -2858,36 +2757,21 @@ __device__ __forceinline__ void rowplan_conv_body(const GcParams &p, char *const
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 float v = (q < 4 ? v0[q] : v1[q - 4]) * sc[q] + sh[q];
-                if (p.residual) v += (float)rh[k % UC][q] + (float)rl[k % UC][q];   // h + l is exact in fp32
+                if (p.residual) v += join_pair(rh[k % UC][q], rl[k % UC][q]);   // h + l is exact in fp32
                 if (p.relu) v = v > 0.f ? v : 0.f;
                 t[q] = v;
-                const uint32_t vb = __float_as_uint(v) & 0x7fffffffu;
-                vmax = (row < p.n_out && vb > vmax) ? vb : vmax;
+                absmax_note(vmax, v, row < p.n_out);
             }
             if (row < p.n_out) {
                 f16x8 h, l;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    h[q] = (_Float16)t[q];
-                    l[q] = (_Float16)(t[q] - (float)h[q]);
-                }
+                split_pair(t, h, l);
                 char *op = reinterpret_cast<char *>(p.out + (size_t)row * p.out_ld) + ((cg >> 2) << 7) + ((cg & 3) << 4);
                 *reinterpret_cast<f16x8 *>(op) = h;
-                *reinterpret_cast<f16x8 *>(op + 64) = l;
+                *reinterpret_cast<f16x8 *>(op + PAIR32_LO) = l;
             }
         }
     }
-    if (p.out_absmax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t t2 = (uint32_t)__shfl_xor((int)vmax, o);
-            vmax = t2 > vmax ? t2 : vmax;
-        }
-        if ((threadIdx.x & 63) == 0) {
-            uint32_t *slot = p.out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-            if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-        }
-    }
+    absmax_raise(p.out_absmax, vmax);
 }
 
 // LDS: [one stage's weights | window | slot table]; the epilogue's EPI_ROWS x (BN + 4) float tile aliases the first two
@@ -2989,8 +2873,8 @@ __global__ void __launch_bounds__(256) pack_weight_f16_kernel(const float *__res
     float v = 0.f;
     if (n < c_out) v = adjoint ? w[((size_t)ts * c_out + n) * c_in + ch] : w[((size_t)ts * c_in + ch) * c_out + n];
     v = v / dsc[n];                                          // * 2^e, exact
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
+    _Float16 h, l;
+    split_pair(v, h, l);
     const size_t blk = ((size_t)t * k32 + kk) * 2;          // (tap, k32) block: 2 pieces x 4 g x np x 8
     const size_t off = ((size_t)g * np + n) * 8 + q;
     ph[(blk + 0) * 4 * np * 8 + off] = h;
@@ -3013,8 +2897,8 @@ __global__ void __launch_bounds__(256) pack_weight_h16_kernel(const float *__res
     const int ch = 4 * g + q, ts = flip ? kv - 1 - t : t;
     float v = 0.f;
     if (n < c_out) v = (adjoint ? w[((size_t)ts * c_out + n) * 16 + ch] : w[((size_t)ts * 16 + ch) * c_out + n]) / dsc[n];       // * 2^e, exact
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
+    _Float16 h, l;
+    split_pair(v, h, l);
     const size_t slot = (((size_t)t * 4 + g) * np + n) * 8;
     ph[slot + q] = h;
     ph[slot + 4 + q] = l;
@@ -3095,6 +2979,31 @@ static void choose_wg_tile(int n_out, int c_in, int c_out, int *bm_out, int *bn_
     if (items >= 2048) { *bm_out = 64; *bn_out = bn; }
 }
 
+// ---- what the launchers ask of their operands ----
+// rows of pitch `ld` floats starting at `ptr` can be addressed in 16-byte pieces (ld 0: one vector, no pitch)
+static bool addr16(const void *ptr, int ld = 0) { return ld % 4 == 0 && ((uintptr_t)ptr & 15) == 0; }
+// `rows` rows of pitch `ld` floats can be read through a buffer resource: num_records and the byte offsets are 32-bit, and a missing
+// neighbour is the index clamped to `rows` -- one row past the end, which must come out as out of range, not wrapped (a page of margin
+// below 4 GB; engine.py applies the same bound before it asks for pair rows)
+static bool fits_buffer_resource(long long rows, int ld) { return (size_t)rows * ld * sizeof(float) < 0xfffff000ull; }
+
+// The fields every conv launch fills the same way, in a zeroed GcParams; the launchers add what is theirs: rulebook, tap masks, row map /
+// column groups and row plan, the split weight image (wb, dsc), img_h / img_w, tiles and items, the pair flags, split > 1 and epi_lds
+static GcParams gc_params(const float *in, int in_ld, int n_in, int c_in, const float *packed_w, int kv, int n_out, int c_out, const float *scale,
+                          const float *shift, const float *residual, int res_ld, int relu, float *out, int out_ld, const uint32_t *in_absmax,
+                          uint32_t *out_absmax) {
+    GcParams p;
+    memset(&p, 0, sizeof p);
+    p.in = in; p.w = packed_w; p.in_absmax = in_absmax; p.out_absmax = out_absmax;
+    p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
+    p.in_ld = in_ld; p.c_in = c_in; p.kc = (c_in + 15) / 16; p.n_in_rows = n_in;
+    p.kv = kv; p.n_out = n_out; p.c_out = c_out; p.ntot = (c_out + 15) / 16; p.np = p.ntot * 16;
+    p.res_ld = res_ld; p.relu = relu; p.out_ld = out_ld;
+    p.n_sub = (n_out + 15) / 16;
+    p.split = 1;
+    return p;
+}
+
 struct GcPlan {
     int use_wg;     // 0: gather_conv_kernel<a,b,vec>, 1: tile_conv_kernel<a,b>, 2: split workgroup kernel, 3: split row-wave kernel
     int a, b, vec;  // (bm,bn) or (ms,nt)
@@ -3112,7 +3021,7 @@ static GcPlan plan(int n_out, int c_in, int c_out, int in_ld, const void *in, in
     GcPlan pl;
     const bool tn = cpd_tuning();
     const int ntot = (c_out + 15) / 16;
-    pl.vec = (c_in % 16 == 0) && (in_ld % 4 == 0) && (((uintptr_t)in & 15) == 0);
+    pl.vec = c_in % 16 == 0 && addr16(in, in_ld);
     pl.use_wg = 0;
     // split path (CPD_GC_BF16X3 / CPD_GC_F16X2): needs whole 32-channel stages
     pl.math = split_math(flags, tn);
@@ -3530,8 +3439,8 @@ __global__ void __launch_bounds__(256) pack_batch_split_kernel(const PackJobDev 
         const int ch = 4 * g + q, ts = j.flip ? j.kv - 1 - t : t;
         float v = 0.f;
         if (n < j.co) v = (j.adjoint ? j.w[((size_t)ts * j.c_in + n) * j.c_out + ch] : j.w[((size_t)ts * j.c_in + ch) * j.c_out + n]) / j.packed[j.off_dsc16 + n];
-        const _Float16 h = (_Float16)v;
-        const _Float16 l = (_Float16)(v - (float)h);
+        _Float16 h, l;
+        split_pair(v, h, l);
         _Float16 *ph = reinterpret_cast<_Float16 *>(j.packed + j.off_h16);
         const size_t slot = (((size_t)t * 4 + g) * j.np + n) * 8;
         ph[slot + q] = h;
@@ -3568,8 +3477,8 @@ __global__ void __launch_bounds__(256) pack_batch_split_kernel(const PackJobDev 
     if (images & 2) {
         _Float16 *ph = reinterpret_cast<_Float16 *>(j.packed + j.off_f16);
         const float vs = v / j.packed[j.off_dsc + n];                 // * 2^e, exact
-        const _Float16 h = (_Float16)vs;
-        const _Float16 l = (_Float16)(vs - (float)h);
+        _Float16 h, l;
+        split_pair(vs, h, l);
         const size_t blk = ((size_t)t * k32 + kk) * 2;
         ph[(blk + 0) * 4 * j.np * 8 + off] = h;
         ph[(blk + 1) * 4 * j.np * 8 + off] = l;
@@ -3701,24 +3610,20 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
     if (n_out == 0) return CPD_OK;
     // fp16-pair rows: whole 32-channel blocks, f16x2 arithmetic, no pre-scaling (a guarded re-run works on fp32 rows)
     const bool in16 = (flags & CPD_GC_IN_PAIRS) && c_in == 16;      // 16-channel pair rows: the wave kernel's K = 16 form
-    if (in16 && (!(flags & CPD_GC_F16X2) || (flags & CPD_GC_DENSE) || (c_out != 16 && c_out != 32) || in_ld % 4 || (((uintptr_t)in) & 15) || in_absmax ||
-                 (size_t)n_in * in_ld * sizeof(float) >= 0xfffff000ull))
+    if (in16 && (!(flags & CPD_GC_F16X2) || (flags & CPD_GC_DENSE) || (c_out != 16 && c_out != 32) || !addr16(in, in_ld) || in_absmax ||
+                 !fits_buffer_resource(n_in, in_ld)))
         return CPD_ERR_UNSUPPORTED;
     if ((flags & CPD_GC_IN_PAIRS) && (flags & CPD_GC_DENSE) && !in16) {
         // DENSE pair rows (round 5: the BEV maps between split-fp16 dense layers): the 128 x 128 pair tile kernel (tile_conv_f16p_kernel) --
         // strided conv through its pixel table, 1 x 1 GEMMs, ConvTranspose(k = s) through the row map / column-group scatter. Pair rows in
         // AND out, no residual, no pre-scaling, no stage split; anything else is refused (nothing else reads dense pair rows)
         if (!(flags & CPD_GC_F16X2) || !(flags & CPD_GC_OUT_PAIRS) || (flags & CPD_GC_RES_PAIRS) || residual || in_absmax || c_in % 32 || c_out % 128 ||
-            in_ld % 4 || out_ld % 4 || (((uintptr_t)in) & 15) || (((uintptr_t)out) & 15) || (out_col_group && out_col_group % 32) ||
-            (size_t)n_in * in_ld * sizeof(float) >= 0xfffff000ull || split_math(flags, cpd_tuning()) != 2)
+            !addr16(in, in_ld) || !addr16(out, out_ld) || (out_col_group && out_col_group % 32) ||
+            !fits_buffer_resource(n_in, in_ld) || split_math(flags, cpd_tuning()) != 2)
             return CPD_ERR_UNSUPPORTED;
-        GcParams p;
-        memset(&p, 0, sizeof p);
-        p.in_pairs = 1; p.out_pairs = 1; p.split = 1;
-        p.in = in; p.w = packed_w; p.out_absmax = out_absmax; p.nbr = nbr; p.scale = scale; p.shift = shift; p.out = out; p.out_row_map = out_row_map;
-        p.in_ld = in_ld; p.c_in = c_in; p.kc = c_in / 16; p.n_in_rows = n_in;
-        p.kv = kv; p.n_out = n_out; p.c_out = c_out; p.ntot = c_out / 16; p.np = c_out;
-        p.relu = relu; p.out_ld = out_ld; p.col_group = out_col_group; p.n_sub = (n_out + 15) / 16;
+        GcParams p = gc_params(in, in_ld, n_in, c_in, packed_w, kv, n_out, c_out, scale, shift, nullptr, 0, relu, out, out_ld, nullptr, out_absmax);
+        p.in_pairs = 1; p.out_pairs = 1;
+        p.nbr = nbr; p.out_row_map = out_row_map; p.col_group = out_col_group;
         p.wb = packed_f16_ptr(packed_w, kv, c_in, c_out);
         p.dsc = packed_dsc_ptr(packed_w, kv, c_in, c_out);
         p.n_rb = (n_out + 127) / 128; p.n_cb = c_out / 128; p.items = p.n_rb * p.n_cb;
@@ -3726,23 +3631,17 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
     }
     if ((flags & CPD_GC_IN_PAIRS) && !in16 &&
         (!(flags & CPD_GC_F16X2) || (flags & CPD_GC_DENSE) || c_in % 32 || c_out % 32 || in_ld % 4 || in_absmax || kv > CPD_RW_TAPS ||
-         (size_t)n_in * in_ld * sizeof(float) >= 0xfffff000ull))
+         !fits_buffer_resource(n_in, in_ld)))
         return CPD_ERR_UNSUPPORTED;
     if ((flags & CPD_GC_OUT_PAIRS) && ((c_out % 32 && c_out != 16) || out_col_group > 0)) return CPD_ERR_UNSUPPORTED;
     if ((flags & CPD_GC_RES_PAIRS) && (!residual || (c_out % 32 && c_out != 16))) return CPD_ERR_ARG;
-    GcParams p;
+    GcParams p = gc_params(in, in_ld, n_in, c_in, packed_w, kv, n_out, c_out, scale, shift, residual, res_ld, relu, out, out_ld, in_absmax, out_absmax);
     p.in_pairs = (flags & CPD_GC_IN_PAIRS) != 0;
     p.out_pairs = (flags & CPD_GC_OUT_PAIRS) ? (c_out == 16 ? 2 : 1) : 0;       // (2: the 16-channel row format)
     p.res_pairs = (flags & CPD_GC_RES_PAIRS) ? (c_out == 16 ? 2 : 1) : 0;
-    p.split = 1; p.part = nullptr;
-    p.plan_slots = nullptr; p.plan_ulist = nullptr; p.plan_count = nullptr;
-    p.in = in; p.w = packed_w; p.wb = nullptr; p.dsc = nullptr; p.in_absmax = in_absmax; p.out_absmax = out_absmax; p.nbr = nbr; p.tapmask = tapmask; p.n_sub = (n_out + 15) / 16; p.scale = scale; p.shift = shift; p.residual = residual;
-    p.out = out; p.out_row_map = out_row_map;
-    p.in_ld = in_ld; p.c_in = c_in; p.kc = (c_in + 15) / 16; p.n_in_rows = n_in;
-    p.kv = kv; p.n_out = n_out; p.c_out = c_out; p.ntot = (c_out + 15) / 16; p.np = p.ntot * 16;
-    p.res_ld = res_ld; p.relu = relu; p.out_ld = out_ld; p.col_group = out_col_group;
+    p.nbr = nbr; p.tapmask = tapmask; p.out_row_map = out_row_map; p.col_group = out_col_group;
     GcPlan pl = plan(n_out, c_in, c_out, in_ld, in, flags);
-    if (pl.use_wg == 3 && (kv > CPD_RW_TAPS || (size_t)n_in * in_ld * sizeof(float) >= 0xfffff000ull))
+    if (pl.use_wg == 3 && (kv > CPD_RW_TAPS || !fits_buffer_resource(n_in, in_ld)))
         pl = plan(n_out, c_in, c_out, in_ld, in, flags | CPD_GC_DENSE);   // the row-wave kernel keeps its taps in 32-bit sets and reads its rows through a 4 GB buffer resource
     if (pl.use_wg == 0 && kv > 32) {
         // the wave kernel keeps a tile's taps in 32-bit sets and their rulebook columns in a 32-tap LDS table: a larger kernel goes to
@@ -3767,9 +3666,8 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
         p.items = p.n_rb * p.n_cb;
     }
     hipStream_t hs = cpd_s(stream);
-    if (part && (pl.use_wg == 3 || pl.use_wg == 2) && !out_col_group && c_out % 4 == 0 && out_ld % 4 == 0 && ((uintptr_t)out & 15) == 0 &&
-        (!residual || (flags & CPD_GC_RES_PAIRS) || (res_ld % 4 == 0 && ((uintptr_t)residual & 15) == 0)) &&
-        (!scale || ((uintptr_t)scale & 15) == 0) && (!shift || ((uintptr_t)shift & 15) == 0)) {
+    if (part && (pl.use_wg == 3 || pl.use_wg == 2) && !out_col_group && c_out % 4 == 0 && addr16(out, out_ld) &&
+        (!residual || (flags & CPD_GC_RES_PAIRS) || addr16(residual, res_ld)) && (!scale || addr16(scale)) && (!shift || addr16(shift))) {
         const int sp = rowwave_split(pl, n_out, c_in, c_out, kv);
         if (sp > 1 && part_bytes >= (size_t)sp * n_out * c_out * sizeof(float)) { p.split = sp; p.part = part; }
     }
@@ -3779,12 +3677,10 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
         if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_RW_EPI")) epi = atoi(e);
         p.epi_lds = epi && pl.use_wg == 3 && pl.a <= 128 && pl.math == 2 && !out_row_map &&
                     (p.in_pairs ? (p.out_pairs == 1 && (!residual || p.res_pairs == 1)) : (p.out_pairs == 0 && p.res_pairs == 0)) &&
-                    !out_col_group && p.split == 1 && out_ld % 4 == 0 && (((uintptr_t)out) & 15) == 0 &&
-                    (!residual || (res_ld % 4 == 0 && (((uintptr_t)residual) & 15) == 0));
+                    !out_col_group && p.split == 1 && addr16(out, out_ld) && (!residual || addr16(residual, res_ld));
     }
     if (pl.use_wg == 2)      // the 128 x 128 split tile kernels' LDS epilogue: 16-byte pieces when the operands allow (element accesses otherwise)
-        p.epi_lds = out_ld % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!out_col_group || out_col_group % 4 == 0) &&
-                    (!residual || (res_ld % 4 == 0 && (((uintptr_t)residual) & 15) == 0));
+        p.epi_lds = addr16(out, out_ld) && (!out_col_group || out_col_group % 4 == 0) && (!residual || addr16(residual, res_ld));
     const GcKernel *k = gather_kernel(pl, in_absmax != nullptr, p.in_pairs, p.epi_lds, in16);
     if (!k) return CPD_ERR_UNSUPPORTED;
     if (pl.use_wg == 2 || pl.use_wg == 3) {
@@ -3806,8 +3702,7 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
         p.dsc = reinterpret_cast<const float *>(p.wb) + packed_h16_image_floats(kv, c_in, c_out);
         int epi = 1;                                 // the level-1 kernels' LDS epilogue (gather_conv_kernel, H16): pair rows out, in place, one column tile
         if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_H16_EPI")) epi = atoi(e);
-        p.epi_lds = epi && pl.b * 16 == c_out && !out_row_map && !out_col_group && out_ld % 4 == 0 && (((uintptr_t)out) & 15) == 0 &&
-                    (!residual || (res_ld % 4 == 0 && (((uintptr_t)residual) & 15) == 0)) &&
+        p.epi_lds = epi && pl.b * 16 == c_out && !out_row_map && !out_col_group && addr16(out, out_ld) && (!residual || addr16(residual, res_ld)) &&
                     ((c_out == 16 && p.out_pairs == 2 && (!residual || p.res_pairs == 2)) ||
                      (c_out == 32 && p.out_pairs == 1 && (!residual || p.res_pairs == 1)));
     }
@@ -3815,7 +3710,7 @@ static int gather_conv_impl(const float *in, int in_ld, int n_in, int c_in, cons
         int epi = 1;
         if (const char *e = cpd_knob(cpd_tuning(), "CPD_GC_H16_EPI")) epi = atoi(e);
         p.epi_lds = epi && pl.b == 1 && c_out == 16 && p.out_pairs == 2 && (!residual || p.res_pairs == 2) && !out_row_map && !out_col_group &&
-                    out_ld % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!residual || (res_ld % 4 == 0 && (((uintptr_t)residual) & 15) == 0));
+                    addr16(out, out_ld) && (!residual || addr16(residual, res_ld));
     }
     p.n_rb = (n_out + 16 * pl.a - 1) / (16 * pl.a);
     p.n_cb = p.ntot / pl.b;
@@ -3884,29 +3779,22 @@ static int conv3x3_rows_impl(const float *in, int in_ld, int frames, int h, int 
         (residual && res_ld < c_out))
         return CPD_ERR_ARG;
     const int bn = window_bn(frames, h, w, c_in, c_out, flags);
-    if (!bn || in_ld % 4 || (((uintptr_t)in) & 15)) return CPD_ERR_UNSUPPORTED;
+    if (!bn || !addr16(in, in_ld)) return CPD_ERR_UNSUPPORTED;
     // 32-bit buffer offsets (the table path takes larger tensors): a row before the tensor's first or after its last must land OUTSIDE
     // num_records and read zeros -- the largest excursion is (w + 1) rows before row 0 / a whole window (<= 258 rows) + w + 1 rows past
     // the last tile's first row, times the row pitch: the tensor plus that distance must stay below 2^32 (size-aware: ADVICE r4)
     if ((size_t)frames * h * w * in_ld * sizeof(float) + ((size_t)w + 1 + 288) * in_ld * sizeof(float) >= 0x100000000ull) return CPD_ERR_UNSUPPORTED;
-    GcParams p;
-    memset(&p, 0, sizeof(p));
     const int n_out = frames * h * w;
     const int math = split_math(flags, cpd_tuning());
-    p.in = in; p.w = packed_w; p.in_absmax = in_absmax; p.out_absmax = out_absmax;
+    GcParams p = gc_params(in, in_ld, n_out, c_in, packed_w, 9, n_out, c_out, scale, shift, residual, res_ld, relu, out, out_ld, in_absmax, out_absmax);
     if (math == 2) { p.wb = packed_f16_ptr(packed_w, 9, c_in, c_out); p.dsc = packed_dsc_ptr(packed_w, 9, c_in, c_out); }
     else p.wb = packed_bf16_ptr(packed_w, 9, c_in, c_out);
-    p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
-    p.in_ld = in_ld; p.c_in = c_in; p.kc = (c_in + 15) / 16;
-    p.kv = 9; p.n_out = n_out; p.c_out = c_out; p.ntot = (c_out + 15) / 16; p.np = p.ntot * 16;
-    p.res_ld = res_ld; p.relu = relu; p.out_ld = out_ld;
-    p.n_sub = (n_out + 15) / 16;
     const int bm = window_bm(frames, h, w, c_out, bn, flags);
     p.n_rb = (n_out + bm - 1) / bm; p.n_cb = (c_out + bn - 1) / bn; p.items = p.n_rb * p.n_cb;
     p.img_h = h; p.img_w = w;
     {
         // the 64- / 128-column tiles' LDS epilogue: 16-byte row pieces when `out` (and `residual`) allow them
-        p.epi_lds = out_ld % 4 == 0 && (((uintptr_t)out) & 15) == 0 && (!residual || (res_ld % 4 == 0 && (((uintptr_t)residual) & 15) == 0));
+        p.epi_lds = addr16(out, out_ld) && (!residual || addr16(residual, res_ld));
         if (bn >= 64 && c_out % bn) return CPD_ERR_UNSUPPORTED;       // (window_bn never picks such a tile)
     }
     if (flags & (CPD_GC_IN_PAIRS | CPD_GC_OUT_PAIRS | CPD_GC_RES_PAIRS)) {
@@ -3953,7 +3841,7 @@ extern "C" int cpd_gather_conv_planned_supported(int n_in, int n_out, int c_in, 
     if (const char *e = cpd_knob(tn, "CPD_GC_PLANNED_MIN")) min_tiles = atoll(e);
     return kv == 27 && (flags & CPD_GC_F16X2) && (flags & CPD_GC_IN_PAIRS) && (flags & CPD_GC_OUT_PAIRS) && !(flags & CPD_GC_DENSE) && c_in % 32 == 0 &&
            (c_out == 32 || c_out == 64 || c_out == 128) && in_ld % 4 == 0 && n_in > 0 && (n_out + 127) / 128 >= min_tiles &&
-           (size_t)n_in * in_ld * sizeof(float) < 0xfffff000ull;          // (rows are read through a 4 GB buffer resource)
+           fits_buffer_resource(n_in, in_ld);                            // (rows are read through a 4 GB buffer resource)
 }
 extern "C" int cpd_gather_conv_planned(const float *in, int in_ld, int n_in, int c_in, const float *packed_w, const uint32_t *tapmask,
                                        const uint16_t *plan_slots, const int32_t *plan_ulist, const int32_t *plan_count, int tile_rows, int kv,
@@ -3964,21 +3852,15 @@ extern "C" int cpd_gather_conv_planned(const float *in, int in_ld, int n_in, int
         return CPD_ERR_ARG;
     if (n_out == 0) return CPD_OK;
     if (tile_rows != 128 && tile_rows != 256) return CPD_ERR_ARG;
-    if (!cpd_gather_conv_planned_supported(n_in, n_out, c_in, c_out, in_ld, kv, flags) || (((uintptr_t)in) & 15)) return CPD_ERR_UNSUPPORTED;
+    if (!cpd_gather_conv_planned_supported(n_in, n_out, c_in, c_out, in_ld, kv, flags) || !addr16(in, in_ld)) return CPD_ERR_UNSUPPORTED;
     if ((flags & CPD_GC_RES_PAIRS) && !residual) return CPD_ERR_ARG;
     if (residual && !(flags & CPD_GC_RES_PAIRS)) return CPD_ERR_UNSUPPORTED;          // (the kernel's epilogue reads pair rows)
-    if ((((uintptr_t)out) & 15) || out_ld % 4 || (residual && ((((uintptr_t)residual) & 15) || res_ld % 4))) return CPD_ERR_UNSUPPORTED;
-    GcParams p;
-    memset(&p, 0, sizeof p);
+    if (!addr16(out, out_ld) || (residual && !addr16(residual, res_ld))) return CPD_ERR_UNSUPPORTED;
+    GcParams p = gc_params(in, in_ld, n_in, c_in, packed_w, kv, n_out, c_out, scale, shift, residual, res_ld, relu, out, out_ld, nullptr, out_absmax);
     p.in_pairs = 1;
     p.out_pairs = (flags & CPD_GC_OUT_PAIRS) ? 1 : 0;
     p.res_pairs = (flags & CPD_GC_RES_PAIRS) ? 1 : 0;
-    p.split = 1;
-    p.in = in; p.w = packed_w; p.out_absmax = out_absmax; p.tapmask = tapmask; p.n_sub = (n_out + 15) / 16;
-    p.scale = scale; p.shift = shift; p.residual = residual; p.out = out;
-    p.in_ld = in_ld; p.c_in = c_in; p.kc = c_in / 16; p.n_in_rows = n_in;
-    p.kv = kv; p.n_out = n_out; p.c_out = c_out; p.ntot = c_out / 16; p.np = c_out;
-    p.res_ld = res_ld; p.relu = relu; p.out_ld = out_ld;
+    p.tapmask = tapmask;
     p.wb = packed_f16_ptr(packed_w, kv, c_in, c_out);
     p.dsc = packed_dsc_ptr(packed_w, kv, c_in, c_out);
     p.plan_slots = plan_slots; p.plan_ulist = plan_ulist; p.plan_count = plan_count;
@@ -4034,7 +3916,7 @@ __global__ void __launch_bounds__(256) absmax_rows_kernel(const float *__restric
         const uint32_t t = (uint32_t)__shfl_xor((int)m, o);
         m = t > m ? t : m;
     }
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(block + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE, m);
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(absmax_slot(block), m);
 }
 extern "C" int cpd_absmax_rows(const float *x, int ld, long long n, int c, uint32_t *absmax_block, cpd_stream_t stream) {
     if (!x || !absmax_block || n < 0 || c <= 0 || ld < c) return CPD_ERR_ARG;

@@ -10,6 +10,7 @@
 // Here 16 lanes share a grid point: they test 16 cells of the scan at a time, a ballot keeps the
 // reference's dz, dy, dx order ("first nsample hits"), and the group stops as soon as nsample
 // neighbours are found. With the bitmap index a cell test is one bit of an L2-resident word.
+#include "absmax.h"
 #include "site_index_layout.h"
 #include "pt_in_box.h"
 
@@ -437,22 +438,12 @@ __global__ void __launch_bounds__(256) voxel_pool_max_mlp_kernel(int m, int nsam
             if (relu) acc = acc > 0.f ? acc : 0.f;
             if (live && co < c2) {
                 out[(size_t)pt * out_ld + co] = acc;
-                const uint32_t vb = __float_as_uint(acc) & 0x7fffffffu;
+                const uint32_t vb = __float_as_uint(acc) & 0x7fffffffu;      // (absmax_note() spelled out: with the helper every instantiation's SGPR count moves by two)
                 vmax = vb > vmax ? vb : vmax;
             }
         }
     }
-    if (out_absmax) {                                                // the range block of the rows written (cpd_gather_conv's `in_absmax` downstream)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint32_t t = (uint32_t)__shfl_xor((int)vmax, o);
-            vmax = t > vmax ? t : vmax;
-        }
-        if ((threadIdx.x & 63) == 0) {
-            uint32_t *slot = out_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE;
-            if (vmax > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, vmax);
-        }
-    }
+    absmax_raise(out_absmax, vmax);                                  // the range block of the rows written (cpd_gather_conv's `in_absmax` downstream)
 }
 
 struct RangeFlagFn {      // mask_points_by_range (common_utils.py:60-63): x, y inside the closed range

@@ -11,6 +11,7 @@
 //     the one-cycle schedule; plain decoupled weight decay).
 // The input gradient itself is cpd_gather_conv again, on transposed (and, for SubM / stride-1
 // convs, tap-flipped) weights with the same or the transposed rulebook.
+#include "absmax.h"
 #include "common.h"
 #include "site_index_layout.h"
 
@@ -246,7 +247,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float *__restri
             // serialise at ~12 ns each (4418 workgroups: +48 us on one word, +1.7 us on 16 lines; a guarding read only adds
             // latency -- tools/atomic_probe.hip)
             m = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
-            atomicMax(dx_absmax + (blockIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE, m);
+            atomicMax(absmax_slot(dx_absmax), m);
         }
     }
 }
@@ -495,28 +496,6 @@ struct WSplitF16x2 {
         return c;
     }
 };
-
-// Power-of-two pre-scale for the fp16 split (same rule as gather_conv.hip): s = 2^(14 - floor(log2 max|x|)), inv = 1 / s
-__device__ __forceinline__ void in_pow2_scale(const uint32_t *absmax, float &s, float &inv) {
-    s = 1.f; inv = 1.f;
-    if (absmax) {
-        // the maximum is kept as CPD_ABSMAX_SLOTS partial maxima, one per 128-byte line (same-line atomics serialise)
-        uint32_t m = absmax[(threadIdx.x & (CPD_ABSMAX_SLOTS - 1)) * CPD_ABSMAX_STRIDE];
-#pragma unroll
-        for (int o = CPD_ABSMAX_SLOTS / 2; o > 0; o >>= 1) {
-            const uint32_t t = (uint32_t)__shfl_xor((int)m, o);
-            m = t > m ? t : m;
-        }
-        m = (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
-        const int e = (int)((m >> 23) & 0xffu);                // biased exponent of max |in|
-        if (e != 0 && e != 255) {                              // zero / denormal / inf / nan maximum: left alone
-            int se = 268 - e;                                  // 127 + 14 - (e - 127)
-            se = se < 1 ? 1 : (se > 253 ? 253 : se);
-            s = __uint_as_float((uint32_t)se << 23);
-            inv = __uint_as_float((uint32_t)(254 - se) << 23);
-        }
-    }
-}
 
 // R rows (4, 8 or 16) of one channel -> the piece images; `slot` = byte offset of k-group k0/8, channel ch
 template <class S, int R, int IMG>
