@@ -171,6 +171,7 @@ SIGNATURES = {
     "cpd_kitti_match_pr": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I, _I,
                                 _I, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_waymo_iou": (_I, [_VP, _VP, _VP, _VP, _VP, _I, ctypes.c_int64, _VP, _VP]),
+    "cpd_waymo_iou_bev": (_I, [_VP, _VP, _VP, _VP, _VP, _I, ctypes.c_int64, _VP, _VP]),
     "cpd_waymo_match_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_waymo_match": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.POINTER(_D), _I, _I, _I, _VP, _VP, _VP,
                              _SZ, _VP]),

@@ -1,7 +1,8 @@
 // waymo_eval.hip -- the hot loops of the Waymo-protocol detection metrics (AP / APH), as cpd_amd/waymo_eval.py defines them
 // (a drop-in for cpd/datasets/waymo_unsupervised/waymo_eval.py, whose metric op lives in a library outside the reference tree):
 //   1. cpd_waymo_iou: the float64 rotated 3-D IoU block (prediction rows x ground-truth columns) of every (frame, type)
-//      problem of a chunk of frames, packed, in one launch;
+//      problem of a chunk of frames, packed, in one launch; cpd_waymo_iou_bev: the same block for the BEV protocol
+//      (waymo_eval2d.py, box_type TYPE_2D: five-column rows, the rectangles' IoU with no z term);
 //   2. cpd_waymo_match: for every problem, the maximum-weight matching at each of the 101 score cut-offs and its counts
 //      (tp / fn per level, fp, heading accuracy), then an ordered reduction over frames.
 //
@@ -43,28 +44,63 @@ constexpr double WM_PI = 3.14159265358979323846;
 
 // ---- IoU ------------------------------------------------------------------------------------------------------------
 
-// the part of a convex polygon with sgn * coordinate[axis] <= lim
+// the part of a convex polygon with sgn * coordinate[axis] <= lim; vertex i of a buffer is element i * S
+template <int S>
 __device__ __forceinline__ int wm_clip(const double *ix, const double *iy, int n, int axis, double sgn, double lim, double *ox,
                                        double *oy) {
     int m = 0;
     for (int i = 0; i < n; ++i) {
         const int k = (i + 1 == n) ? 0 : i + 1;
-        const double px = ix[i], py = iy[i], qx = ix[k], qy = iy[k];
+        const double px = ix[i * S], py = iy[i * S], qx = ix[k * S], qy = iy[k * S];
         const double fp = lim - sgn * (axis ? py : px), fq = lim - sgn * (axis ? qy : qx);
         const bool pin = fp >= 0.0, qin = fq >= 0.0;
         if (pin && m < WM_MAX_PTS) {
-            ox[m] = px;
-            oy[m] = py;
+            ox[m * S] = px;
+            oy[m * S] = py;
             ++m;
         }
         if (pin != qin && m < WM_MAX_PTS) {          // fp and fq differ in sign, so fp - fq is not zero
             const double t = fp / (fp - fq);
-            ox[m] = px + t * (qx - px);
-            oy[m] = py + t * (qy - py);
+            ox[m * S] = px + t * (qx - px);
+            oy[m * S] = py + t * (qy - py);
             ++m;
         }
     }
     return m;
+}
+
+// area of the intersection of rectangle A (centre, full sizes, heading) with rectangle B: A's corners go into B's frame, where
+// B is [-dx/2, dx/2] x [-dy/2, dy/2], and are clipped by its four half-planes; 0 when no circle of A reaches B's or fewer than
+// 3 vertices remain. px, py, qx, qy: the caller's four buffers of WM_MAX_PTS vertices, vertex i at element i * S.
+template <int S>
+__device__ __forceinline__ double wm_rect_overlap(double ax, double ay, double adx, double ady, double ah, double bx, double by,
+                                                  double bdx, double bdy, double bh, double *px, double *py, double *qx,
+                                                  double *qy) {
+    const double hxa = adx / 2.0, hya = ady / 2.0, hxb = bdx / 2.0, hyb = bdy / 2.0;
+    const double tx = ax - bx, ty = ay - by;
+    // no circle of A reaches B's: nothing to clip
+    const double reach = sqrt(hxa * hxa + hya * hya) + sqrt(hxb * hxb + hyb * hyb);
+    if (tx * tx + ty * ty > reach * reach) return 0.0;
+    const double cb = cos(bh), sb = sin(bh);
+    const double lx = cb * tx + sb * ty, ly = cb * ty - sb * tx;      // A's centre in B's frame
+    const double d = ah - bh, c = cos(d), s = sin(d);
+    const double sxs[4] = {1.0, -1.0, -1.0, 1.0}, sys[4] = {1.0, 1.0, -1.0, -1.0};
+    for (int i = 0; i < 4; ++i) {
+        const double ex = sxs[i] * hxa, ey = sys[i] * hya;
+        px[i * S] = lx + (c * ex - s * ey);
+        py[i * S] = ly + (s * ex + c * ey);
+    }
+    int n = wm_clip<S>(px, py, 4, 0, 1.0, hxb, qx, qy);
+    n = wm_clip<S>(qx, qy, n, 0, -1.0, hxb, px, py);
+    n = wm_clip<S>(px, py, n, 1, 1.0, hyb, qx, qy);
+    n = wm_clip<S>(qx, qy, n, 1, -1.0, hyb, px, py);
+    if (n < 3) return 0.0;
+    double twice = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int k = (i + 1 == n) ? 0 : i + 1;
+        twice += px[i * S] * py[k * S] - px[k * S] * py[i * S];
+    }
+    return fabs(twice) / 2.0;
 }
 
 // rows (cx, cy, cz, dx, dy, dz, heading) float32; 0 for an empty intersection, a non-positive union or any non-finite value
@@ -80,33 +116,35 @@ __device__ __forceinline__ double wm_iou(const float *pa, const float *pb) {
     const double zlo = fmax(a[2] - a[5] / 2.0, b[2] - b[5] / 2.0), zhi = fmin(a[2] + a[5] / 2.0, b[2] + b[5] / 2.0);
     const double h = zhi - zlo;
     if (!(h > 0.0)) return 0.0;
-    const double hxa = a[3] / 2.0, hya = a[4] / 2.0, hxb = b[3] / 2.0, hyb = b[4] / 2.0;
-    const double tx = a[0] - b[0], ty = a[1] - b[1];
-    // no circle of A reaches B's: nothing to clip
-    const double reach = sqrt(hxa * hxa + hya * hya) + sqrt(hxb * hxb + hyb * hyb);
-    if (tx * tx + ty * ty > reach * reach) return 0.0;
-    const double cb = cos(b[6]), sb = sin(b[6]);
-    const double lx = cb * tx + sb * ty, ly = cb * ty - sb * tx;      // A's centre in B's frame
-    const double d = a[6] - b[6], c = cos(d), s = sin(d);
     double px[WM_MAX_PTS], py[WM_MAX_PTS], qx[WM_MAX_PTS], qy[WM_MAX_PTS];
-    const double sxs[4] = {1.0, -1.0, -1.0, 1.0}, sys[4] = {1.0, 1.0, -1.0, -1.0};
-    for (int i = 0; i < 4; ++i) {
-        const double ex = sxs[i] * hxa, ey = sys[i] * hya;
-        px[i] = lx + (c * ex - s * ey);
-        py[i] = ly + (s * ex + c * ey);
-    }
-    int n = wm_clip(px, py, 4, 0, 1.0, hxb, qx, qy);
-    n = wm_clip(qx, qy, n, 0, -1.0, hxb, px, py);
-    n = wm_clip(px, py, n, 1, 1.0, hyb, qx, qy);
-    n = wm_clip(qx, qy, n, 1, -1.0, hyb, px, py);
-    if (n < 3) return 0.0;
-    double twice = 0.0;
-    for (int i = 0; i < n; ++i) {
-        const int k = (i + 1 == n) ? 0 : i + 1;
-        twice += px[i] * py[k] - px[k] * py[i];
-    }
-    const double inter = fabs(twice) / 2.0 * h;
+    const double inter = wm_rect_overlap<1>(a[0], a[1], a[3], a[4], a[6], b[0], b[1], b[3], b[4], b[6], px, py, qx, qy) * h;
     const double uni = a[3] * a[4] * a[5] + b[3] * b[4] * b[5] - inter;
+    if (!(inter > 0.0) || !(uni > 0.0)) return 0.0;
+    const double v = inter / uni;
+    return isfinite(v) ? v : 0.0;
+}
+
+// rows (cx, cy, dx, dy, heading) float32, the boxes of box_type TYPE_2D: the rectangles' intersection over their union, no z
+// term. 0 for an empty intersection, a non-positive union, a size that is not positive (two negative ones would pass for a
+// box), and any value that is not finite or not below WM_BEV_LIMIT in magnitude (2^29: a float32 that large holds neither a
+// position in metres nor a direction, its ulp is 32). The four vertex buffers are the block's LDS, one column per lane, so
+// the vertex counts that index them cost no scratch: WM_THREADS * 4 * WM_MAX_PTS doubles, 64 KiB.
+constexpr double WM_BEV_LIMIT = 0x1.0p+29;
+__device__ __forceinline__ double wm_iou_bev(const float *pa, const float *pb) {
+    double a[5], b[5];
+    bool ok = true;
+    for (int i = 0; i < 5; ++i) {
+        a[i] = (double)pa[i];
+        b[i] = (double)pb[i];
+        ok = ok && fabs(a[i]) < WM_BEV_LIMIT && fabs(b[i]) < WM_BEV_LIMIT;      // false for NaN and the infinities too
+    }
+    if (!ok || !(a[2] > 0.0 && a[3] > 0.0 && b[2] > 0.0 && b[3] > 0.0)) return 0.0;
+    __shared__ double poly[4][WM_MAX_PTS][WM_THREADS];
+    double *mine = &poly[0][0][threadIdx.x];
+    constexpr int BUF = WM_MAX_PTS * WM_THREADS;
+    const double inter = wm_rect_overlap<WM_THREADS>(a[0], a[1], a[2], a[3], a[4], b[0], b[1], b[2], b[3], b[4], mine, mine + BUF,
+                                                     mine + 2 * BUF, mine + 3 * BUF);
+    const double uni = a[2] * a[3] + b[2] * b[3] - inter;
     if (!(inter > 0.0) || !(uni > 0.0)) return 0.0;
     const double v = inter / uni;
     return isfinite(v) ? v : 0.0;
@@ -121,8 +159,9 @@ struct WmIouArgs {
     double *out;
 };
 
-// one lane per packed (problem, prediction row, ground-truth column), grid-stride
-__global__ void __launch_bounds__(WM_THREADS) waymo_iou_kernel(WmIouArgs a) {
+// one lane per packed (problem, prediction row, ground-truth column), grid-stride; STRIDE floats per row, PAIR their IoU
+template <int STRIDE, double (*PAIR)(const float *, const float *)>
+__device__ __forceinline__ void wm_iou_lanes(const WmIouArgs &a) {
     for (int64_t p = (int64_t)blockIdx.x * WM_THREADS + threadIdx.x; p < a.n_pairs; p += (int64_t)gridDim.x * WM_THREADS) {
         int lo = 0, hi = a.n_problems;              // pair_off[lo] <= p < pair_off[hi]; empty problems share an offset
         for (int it = 0; it < 32 && hi - lo > 1; ++it) {
@@ -133,9 +172,11 @@ __global__ void __launch_bounds__(WM_THREADS) waymo_iou_kernel(WmIouArgs a) {
         const int64_t r = p - a.pair_off[lo];
         const int ng = a.gt_off[lo + 1] - a.gt_off[lo];
         const int i = a.pd_off[lo] + (int)(r / ng), j = a.gt_off[lo] + (int)(r % ng);
-        a.out[p] = wm_iou(a.pd + 7 * (int64_t)i, a.gt + 7 * (int64_t)j);
+        a.out[p] = PAIR(a.pd + STRIDE * (int64_t)i, a.gt + STRIDE * (int64_t)j);
     }
 }
+__global__ void __launch_bounds__(WM_THREADS) waymo_iou_kernel(WmIouArgs a) { wm_iou_lanes<7, wm_iou>(a); }
+__global__ void __launch_bounds__(WM_THREADS) waymo_iou_bev_kernel(WmIouArgs a) { wm_iou_lanes<5, wm_iou_bev>(a); }
 
 // ---- matching -------------------------------------------------------------------------------------------------------
 
@@ -414,8 +455,10 @@ WmLayout wm_layout(int n_problems, int total_pd) {
 
 }  // namespace
 
-extern "C" int cpd_waymo_iou(const float *pd_boxes, const float *gt_boxes, const int32_t *pd_off, const int32_t *gt_off,
-                             const int64_t *pair_off, int n_problems, int64_t n_pairs, double *out, cpd_stream_t st) {
+// the two IoU entry points differ in the kernel alone
+static int wm_launch_iou(void (*kernel)(WmIouArgs), const char *label, const float *pd_boxes, const float *gt_boxes,
+                         const int32_t *pd_off, const int32_t *gt_off, const int64_t *pair_off, int n_problems, int64_t n_pairs,
+                         double *out, cpd_stream_t st) {
     if (n_problems <= 0 || n_pairs < 0 || !pd_off || !gt_off || !pair_off) return CPD_ERR_ARG;
     if (n_pairs == 0) return CPD_OK;
     if (!pd_boxes || !gt_boxes || !out) return CPD_ERR_ARG;
@@ -423,10 +466,22 @@ extern "C" int cpd_waymo_iou(const float *pd_boxes, const float *gt_boxes, const
     WmIouArgs a;
     a.pd = pd_boxes; a.gt = gt_boxes; a.pd_off = pd_off; a.gt_off = gt_off; a.pair_off = pair_off;
     a.n_problems = n_problems; a.n_pairs = n_pairs; a.out = out;
-    cpd_launch_log_note("waymo_iou_kernel");
+    cpd_launch_log_note(label);
     const int64_t blocks = (n_pairs + WM_THREADS - 1) / WM_THREADS;     // capped: the kernel strides over the rest
-    waymo_iou_kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), WM_THREADS, 0, cpd_s(st)>>>(a);
+    kernel<<<(unsigned)(blocks < 65536 ? blocks : 65536), WM_THREADS, 0, cpd_s(st)>>>(a);
     return cpd_check_launch();
+}
+
+extern "C" int cpd_waymo_iou(const float *pd_boxes, const float *gt_boxes, const int32_t *pd_off, const int32_t *gt_off,
+                             const int64_t *pair_off, int n_problems, int64_t n_pairs, double *out, cpd_stream_t st) {
+    return wm_launch_iou(waymo_iou_kernel, "waymo_iou_kernel", pd_boxes, gt_boxes, pd_off, gt_off, pair_off, n_problems, n_pairs,
+                         out, st);
+}
+
+extern "C" int cpd_waymo_iou_bev(const float *pd_boxes, const float *gt_boxes, const int32_t *pd_off, const int32_t *gt_off,
+                                 const int64_t *pair_off, int n_problems, int64_t n_pairs, double *out, cpd_stream_t st) {
+    return wm_launch_iou(waymo_iou_bev_kernel, "waymo_iou_bev_kernel", pd_boxes, gt_boxes, pd_off, gt_off, pair_off, n_problems,
+                         n_pairs, out, st);
 }
 
 extern "C" size_t cpd_waymo_match_workspace_bytes(int n_problems, int total_pd) {

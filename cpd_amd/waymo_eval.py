@@ -46,6 +46,13 @@ once. There is no per-frame Python loop. Limits: at most CPD_WAYMO_MAX_PD = 4096
 ground truths per (frame, type); beyond them CpdHipError (CPD_ERR_UNSUPPORTED). No GPU raises CpdHipError: there is no
 CPU fallback.
 
+OTHER BOX TYPE, OTHER THRESHOLDS. evaluate_arrays(..., box_type='TYPE_2D') is the BEV protocol of waymo_eval2d.py (rows
+(cx, cy, dx, dy, heading), cpd_waymo_iou_bev, own thresholds 0.5 / 0.3 / 0.3 / 0.3; cpd_amd.waymo_eval2d is its drop-in).
+iou_thresholds= replaces the protocol's set by one set of 4 or by a sequence of S sets; with S sets every chunk's IoU block
+is still computed once and cpd_waymo_match runs once per set over it, into that set's totals (results get a leading axis
+S). OpenPCDetWaymoDetectionMetricsEstimator.waymo_evaluation_at(..., iou_thresholds) returns one result dict per set, e.g.
+vehicle AP at IoU 0.7 and at 0.5 from one pass. The defaults are the protocol above, bit for bit.
+
 Differences from the reference's host code, all deliberate: generate_waymo_type_results does not modify the caller's
 infos (the reference rewrites info['difficulty'] and info['gt_boxes_lidar'] in place; Dataset.evaluation passes deep
 copies anyway), and a prediction set with no boxes at all evaluates to zeros where the reference's pd_score.max() raises.
@@ -58,6 +65,9 @@ from . import _lib
 N_CUTOFFS = 101
 N_TYPES = 4
 IOU_THRESHOLDS = (0.7, 0.5, 0.5, 0.5)          # type ids 1..4 (build_config's iou_thresholds[1:])
+# box_type -> (row width, heading column, IoU entry point, the protocol's own thresholds): waymo_eval.py and waymo_eval2d.py
+BOX_TYPES = {'TYPE_3D': (7, 6, 'cpd_waymo_iou', IOU_THRESHOLDS),
+             'TYPE_2D': (5, 4, 'cpd_waymo_iou_bev', (0.5, 0.3, 0.3, 0.3))}
 TYPE_NAMES = ('VEHICLE', 'PEDESTRIAN', 'SIGN', 'CYCLIST')
 LEVELS = (1, 2)
 MAX_PD, MAX_GT = 4096, 1024                    # CPD_WAYMO_MAX_PD / CPD_WAYMO_MAX_GT
@@ -108,11 +118,11 @@ def _offsets(counts, dtype):
     return off.astype(dtype)
 
 
-def _checked(name, frame_id, boxes, obj_type, n_frames, **per_box):
+def _checked(name, frame_id, boxes, obj_type, n_frames, width=7, **per_box):
     """The op's inputs with the casts of its placeholders (float32 boxes / scores, uint8 types / difficulties)."""
     boxes = np.asarray(boxes)
-    if boxes.ndim != 2 or boxes.shape[1] != 7:
-        raise ValueError("waymo_eval: %s boxes must be [N, 7], got %s" % (name, boxes.shape))
+    if boxes.ndim != 2 or boxes.shape[1] != width:
+        raise ValueError("waymo_eval: %s boxes must be [N, %d], got %s" % (name, width, boxes.shape))
     if boxes.dtype.kind not in "fiu":
         raise TypeError("waymo_eval: %s boxes must be numeric, got %s" % (name, boxes.dtype))
     n = boxes.shape[0]
@@ -157,22 +167,49 @@ def _chunks(pairs_per_frame, chunk_frames, pair_budget):
     return bounds
 
 
+def _threshold_sets(iou_thresholds, default):
+    """(the sets as a list of 4-tuples of float, whether the caller gave a sequence of sets and not one set)."""
+    if iou_thresholds is None:
+        iou_thresholds = default
+    if iou_thresholds is None:
+        raise ValueError("waymo_eval: no IoU threshold set")
+    sets = list(iou_thresholds)
+    stacked = bool(sets) and not np.isscalar(sets[0])
+    sets = [tuple(float(v) for v in one) for one in sets] if stacked else [tuple(float(v) for v in sets)]
+    if not sets:
+        raise ValueError("waymo_eval: no IoU threshold set")
+    for one in sets:
+        if len(one) != N_TYPES:
+            raise ValueError("waymo_eval: a threshold set has one value per type id 1..%d, got %d" % (N_TYPES, len(one)))
+        if not all(0.0 < v <= 1.0 for v in one):
+            raise ValueError("waymo_eval: IoU thresholds must lie in (0, 1], got %s" % (one,))
+    return sets, stacked
+
+
 def evaluate_arrays(pd_frame, pd_boxes, pd_type, pd_score, gt_frame, gt_boxes, gt_type, gt_difficulty, n_frames,
-                    chunk_frames=None, pair_budget=PAIR_BUDGET):
+                    chunk_frames=None, pair_budget=PAIR_BUDGET, box_type='TYPE_3D', iou_thresholds=None):
     """The metric op's part: counts [4 types][2 levels][101 cut-offs][tp, fp, fn] int64 and heading-accuracy sums
-    [4][2][101] float64 of the given predictions and ground truths (frame ids 0..n_frames-1, types 0..255)."""
+    [4][2][101] float64 of the given predictions and ground truths (frame ids 0..n_frames-1, types 0..255).
+    `box_type`: 'TYPE_3D' (rows [N, 7], rotated 3-D IoU) or 'TYPE_2D' (rows [N, 5] = (cx, cy, dx, dy, heading), the
+    rectangles' IoU). `iou_thresholds`: None for the protocol's own set, one set of 4 (type ids 1..4), or a sequence of S
+    sets -- then both results get a leading axis S; every chunk's IoU block is computed once and matched once per set."""
+    if box_type not in BOX_TYPES:
+        raise ValueError("waymo_eval: box_type must be one of %s, got %r" % (sorted(BOX_TYPES), box_type))
+    width, heading_col, iou_entry, own_thresholds = BOX_TYPES[box_type]
+    sets, stacked = _threshold_sets(iou_thresholds, own_thresholds)
     n_frames = int(n_frames)
     if n_frames < 0:
         raise ValueError("waymo_eval: n_frames is %d" % n_frames)
-    pd = _checked("prediction", pd_frame, pd_boxes, pd_type, n_frames, score=(pd_score, np.float32))
-    gt = _checked("ground-truth", gt_frame, gt_boxes, gt_type, n_frames, difficulty=(gt_difficulty, np.uint8))
+    pd = _checked("prediction", pd_frame, pd_boxes, pd_type, n_frames, width, score=(pd_score, np.float32))
+    gt = _checked("ground-truth", gt_frame, gt_boxes, gt_type, n_frames, width, difficulty=(gt_difficulty, np.uint8))
     if np.isnan(pd["score"]).any():
         raise ValueError("waymo_eval: NaN prediction score")
     dev = _device()
-    counts = torch.zeros((N_TYPES, 2, N_CUTOFFS, 3), dtype=torch.int64, device=dev)
-    ha = torch.zeros((N_TYPES, 2, N_CUTOFFS), dtype=torch.float64, device=dev)
+    counts = torch.zeros((len(sets), N_TYPES, 2, N_CUTOFFS, 3), dtype=torch.int64, device=dev)
+    ha = torch.zeros((len(sets), N_TYPES, 2, N_CUTOFFS), dtype=torch.float64, device=dev)
     if n_frames == 0:
-        return counts.cpu().numpy(), ha.cpu().numpy()
+        counts, ha = counts.cpu().numpy(), ha.cpu().numpy()
+        return (counts, ha) if stacked else (counts[0], ha[0])
     pd, pd_n = _grouped(pd, n_frames)
     gt, gt_n = _grouped(gt, n_frames)
     if pd_n.max(initial=0) > MAX_PD or gt_n.max(initial=0) > MAX_GT:
@@ -183,10 +220,12 @@ def evaluate_arrays(pd_frame, pd_boxes, pd_type, pd_score, gt_frame, gt_boxes, g
         raise _lib.CpdHipError("waymo_eval: more than 2^31 boxes")
     pairs = pd_n * gt_n
     d_pd_boxes, d_gt_boxes = _to_dev(pd["boxes"], np.float32), _to_dev(gt["boxes"], np.float32)
-    d_pd_head, d_gt_head = _to_dev(pd["boxes"][:, 6], np.float32), _to_dev(gt["boxes"][:, 6], np.float32)
+    d_pd_head, d_gt_head = (_to_dev(pd["boxes"][:, heading_col], np.float32),
+                            _to_dev(gt["boxes"][:, heading_col], np.float32))
     d_score, d_diff = _to_dev(pd["score"], np.float32), _to_dev(gt["difficulty"], np.uint8)
-    thr = (_lib._D * N_TYPES)(*IOU_THRESHOLDS)
+    thr = [(_lib._D * N_TYPES)(*one) for one in sets]
     lib, P = _lib.lib(), _lib.ptr
+    iou_fn = getattr(lib, iou_entry)
     for c, (f0, f1) in enumerate(_chunks(pairs.reshape(n_frames, N_TYPES).sum(1), chunk_frames, pair_budget)):
         q0, q1 = f0 * N_TYPES, f1 * N_TYPES
         p0, p1, g0, g1 = int(pd_off[q0]), int(pd_off[q1]), int(gt_off[q0]), int(gt_off[q1])
@@ -195,18 +234,19 @@ def evaluate_arrays(pd_frame, pd_boxes, pd_type, pd_score, gt_frame, gt_boxes, g
         d_poff, d_goff = _to_dev(pd_off[q0:q1 + 1] - p0, np.int32), _to_dev(gt_off[q0:q1 + 1] - g0, np.int32)
         d_pair_off = _to_dev(pair_off, np.int64)
         iou = torch.empty(max(n_pairs, 1), dtype=torch.float64, device=dev)
-        _lib.check(lib.cpd_waymo_iou(P(d_pd_boxes[p0:p1]), P(d_gt_boxes[g0:g1]), P(d_poff), P(d_goff), P(d_pair_off),
-                                     q1 - q0, n_pairs, P(iou), _lib.stream()), "cpd_waymo_iou")
+        _lib.check(iou_fn(P(d_pd_boxes[p0:p1]), P(d_gt_boxes[g0:g1]), P(d_poff), P(d_goff), P(d_pair_off),
+                          q1 - q0, n_pairs, P(iou), _lib.stream()), iou_entry)
         ws_bytes = lib.cpd_waymo_match_workspace_bytes(q1 - q0, p1 - p0)
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        _lib.check(lib.cpd_waymo_match(P(iou), P(d_pair_off), P(d_poff), P(d_goff), q1 - q0, p1 - p0, g1 - g0,
-                                       P(d_score[p0:p1]), P(d_diff[g0:g1]), P(d_pd_head[p0:p1]), P(d_gt_head[g0:g1]), thr,
-                                       int(pd_n[q0:q1].max()), int(gt_n[q0:q1].max()), int(c > 0), P(counts), P(ha),
-                                       P(ws), ws_bytes, _lib.stream()), "cpd_waymo_match")
+        for s in range(len(sets)):                  # the same IoU block under every threshold set, in stream order
+            _lib.check(lib.cpd_waymo_match(P(iou), P(d_pair_off), P(d_poff), P(d_goff), q1 - q0, p1 - p0, g1 - g0,
+                                           P(d_score[p0:p1]), P(d_diff[g0:g1]), P(d_pd_head[p0:p1]), P(d_gt_head[g0:g1]),
+                                           thr[s], int(pd_n[q0:q1].max()), int(gt_n[q0:q1].max()), int(c > 0),
+                                           P(counts[s]), P(ha[s]), P(ws), ws_bytes, _lib.stream()), "cpd_waymo_match")
     counts, ha = counts.cpu().numpy(), ha.cpu().numpy()
     if counts.min() < 0:
         raise _lib.CpdHipError("cpd_waymo_match: a problem exceeded the maxima passed to it")
-    return counts, ha
+    return (counts, ha) if stacked else (counts[0], ha[0])
 
 
 def result_dict(counts, ha):
@@ -223,6 +263,8 @@ def result_dict(counts, ha):
 
 class OpenPCDetWaymoDetectionMetricsEstimator:
     WAYMO_CLASSES = ['unknown', 'Vehicle', 'Pedestrian', 'Truck', 'Cyclist']
+    BOX_TYPE = 'TYPE_3D'
+    BOX_COLUMNS = None          # the columns of the seven-column boxes that the op is fed: all (waymo_eval2d: [0, 1, 3, 4, 6])
 
     def generate_waymo_type_results(self, infos, class_names, is_gt=False, fake_gt_infos=True):
         """(frame_id int64, boxes3d, obj_type, score, overlap_nlz, difficulty int8) of waymo_eval.py:26-84. Unlike the
@@ -251,13 +293,14 @@ class OpenPCDetWaymoDetectionMetricsEstimator:
                     w, l, h, r = gt_boxes[:, 3:4], gt_boxes[:, 4:5], gt_boxes[:, 5:6], gt_boxes[:, 6:7]
                     gt_boxes[:, 2] += h[:, 0] / 2
                     gt_boxes = np.concatenate([gt_boxes[:, 0:3], l, w, h, -(r + np.pi / 2)], axis=-1)
-                boxes3d.append(gt_boxes[box_mask])
+                boxes = gt_boxes[box_mask]
             else:
                 num_boxes = len(info['boxes_lidar'])
                 difficulty.append([0] * num_boxes)
                 score.append(info['score'])
-                boxes3d.append(np.array(info['boxes_lidar']))
+                boxes = np.array(info['boxes_lidar'])
                 box_name = info['name']
+            boxes3d.append(boxes if self.BOX_COLUMNS is None else boxes[:, self.BOX_COLUMNS])
             obj_type += [self.WAYMO_CLASSES.index(name) for name in box_name]
             frame_id.append(np.array([frame_index] * num_boxes))
             overlap_nlz.append(np.zeros(num_boxes))
@@ -276,8 +319,8 @@ class OpenPCDetWaymoDetectionMetricsEstimator:
             'breakdown_generator_ids': ['OBJECT_TYPE'],
             'difficulties': {'levels': list(LEVELS)},
             'matcher_type': 'TYPE_HUNGARIAN',
-            'iou_thresholds': [0.0] + list(IOU_THRESHOLDS),
-            'box_type': 'TYPE_3D',
+            'iou_thresholds': [0.0] + list(BOX_TYPES[self.BOX_TYPE][3]),
+            'box_type': self.BOX_TYPE,
             'score_cutoffs': [x * 0.01 for x in range(0, 100)] + [1.0],
         }
 
@@ -290,10 +333,28 @@ class OpenPCDetWaymoDetectionMetricsEstimator:
         return tuple(ret_ans)
 
     def waymo_evaluation(self, prediction_infos, gt_infos, class_name, distance_thresh=100, fake_gt_infos=True,
-                         detail=None, chunk_frames=None):
+                         detail=None, chunk_frames=None, pair_budget=PAIR_BUDGET):
         """waymo_eval.py:178-216. `detail`, when a dict, receives the raw per-cut-off counts: 'counts' [4][2][101][3]
         int64 (tp, fp, fn), 'ha' [4][2][101] float64 and 'score_cutoffs' [101] float32. `chunk_frames` caps the frames
-        per GPU chunk (the pair budget always applies); the result does not depend on it."""
+        per GPU chunk and `pair_budget` its packed pairs; the result depends on neither."""
+        counts, ha = self._counts(prediction_infos, gt_infos, class_name, distance_thresh, fake_gt_infos, None, detail,
+                                  chunk_frames, pair_budget)
+        return result_dict(counts, ha)
+
+    def waymo_evaluation_at(self, prediction_infos, gt_infos, class_name, iou_thresholds, distance_thresh=100,
+                            fake_gt_infos=True, detail=None, chunk_frames=None, pair_budget=PAIR_BUDGET):
+        """waymo_evaluation under each of the given IoU threshold sets (a sequence of sets of 4, type ids 1..4; e.g.
+        vehicle AP at 0.5 and at 0.7): a list of result dicts, one per set, for one pass over the IoU blocks. `detail`
+        receives 'counts' [S][4][2][101][3] and 'ha' [S][4][2][101]."""
+        sets, stacked = _threshold_sets(iou_thresholds, None)
+        if not stacked:
+            raise ValueError("waymo_eval: waymo_evaluation_at takes a sequence of threshold sets")
+        counts, ha = self._counts(prediction_infos, gt_infos, class_name, distance_thresh, fake_gt_infos, sets, detail,
+                                  chunk_frames, pair_budget)
+        return [result_dict(c, h) for c, h in zip(counts, ha)]
+
+    def _counts(self, prediction_infos, gt_infos, class_name, distance_thresh, fake_gt_infos, iou_thresholds, detail,
+                chunk_frames, pair_budget):
         print('Start the waymo evaluation...')
 
         assert len(prediction_infos) == len(gt_infos), '%d vs %d' % (prediction_infos.__len__(), gt_infos.__len__())
@@ -320,7 +381,8 @@ class OpenPCDetWaymoDetectionMetricsEstimator:
             print('Warning: Waymo evaluation only supports normalized scores')
 
         counts, ha = evaluate_arrays(pd_frameid, pd_boxes3d, pd_type, pd_score, gt_frameid, gt_boxes3d, gt_type,
-                                     gt_difficulty, len(gt_infos), chunk_frames=chunk_frames)
+                                     gt_difficulty, len(gt_infos), chunk_frames=chunk_frames, pair_budget=pair_budget,
+                                     box_type=self.BOX_TYPE, iou_thresholds=iou_thresholds)
         if detail is not None:
             detail['counts'], detail['ha'], detail['score_cutoffs'] = counts, ha, SCORE_CUTOFFS.copy()
-        return result_dict(counts, ha)
+        return counts, ha

@@ -1016,6 +1016,15 @@ int cpd_kitti_match_pr(const double *overlaps, const int64_t *pair_off, const in
  * the z overlap over the union; 0 for an empty intersection, a non-positive union or a non-finite value. out [n_pairs] float64. */
 int cpd_waymo_iou(const float *pd_boxes, const float *gt_boxes, const int32_t *pd_off, const int32_t *gt_off,
                   const int64_t *pair_off, int n_problems, int64_t n_pairs, double *out, cpd_stream_t stream);
+/* The same for the BEV protocol (cpd/datasets/waymo_unsupervised/waymo_eval2d.py:63,69,87-102: box_type TYPE_2D, the boxes are
+ * columns [0, 1, 3, 4, 6], thresholds 0.5 / 0.3 / 0.3 / 0.3): rows (cx, cy, dx, dy, heading) float32, stride 5, dx along the
+ * heading; float64 arithmetic; area of the two rotated rectangles' intersection over dx_a dy_a + dx_b dy_b - that area, with no
+ * z term: boxes one above the other overlap. 0 for an empty intersection, fewer than 3 clipped vertices, a non-positive union,
+ * a size that is not positive, a non-finite value, and any value of magnitude 2^29 or more (which holds neither a position nor
+ * a direction in float32).
+ * Same packing and arguments as cpd_waymo_iou; cpd_waymo_match takes the block as it is, with column 4 as the headings. */
+int cpd_waymo_iou_bev(const float *pd_boxes, const float *gt_boxes, const int32_t *pd_off, const int32_t *gt_off,
+                      const int64_t *pair_off, int n_problems, int64_t n_pairs, double *out, cpd_stream_t stream);
 /* Workspace of cpd_waymo_match (HOST): the score order of total_pd predictions and 101 per-problem results. */
 size_t cpd_waymo_match_workspace_bytes(int n_problems, int total_pd);
 /* The counts the metric op accumulates for waymo_evaluation (l.206-215): per problem and cut-off k the maximum-weight matching
