@@ -165,6 +165,10 @@ SIGNATURES = {
     "cpd_rcnn_loss": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _I, _FP, _F, _F, _F, _I, _VP, _VP, _VP, _VP]),
     "cpd_rcnn_proto_loss": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _FP, _F, _F, _F, _F, _F, _I,
                                  _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "cpd_roi_targets_workspace_bytes": (_SZ, [_I, _I]),
+    "cpd_roi_targets_classify": (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _FP, _FP, _I, _F, _VP, _VP, _SZ, _VP]),
+    "cpd_roi_targets_gather": (_I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, ctypes.POINTER(_VP), _VP, _I, _VP, _VP, _SZ, _I, _I, _FP, _FP, _FP,
+                                    _FP, _FP, _I3, _I3, _FP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, ctypes.POINTER(_VP), _VP]),
     "cpd_kitti_overlaps": (_I, [_I, _I, _VP, _VP, _VP, _VP, _VP, _I, ctypes.c_int64, _VP, _VP]),
     "cpd_kitti_match_workspace_bytes": (_SZ, [_I, _I, _I]),
     "cpd_kitti_match_scores": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),

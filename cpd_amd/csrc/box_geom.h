@@ -1,4 +1,5 @@
-// box_geom.h -- rotated-box BEV geometry shared by iou3d_nms.hip (pairwise matrices, NMS) and atss.hip (ATSS assigner).
+// box_geom.h -- rotated-box BEV geometry shared by iou3d_nms.hip (pairwise matrices, NMS, recall), atss.hip (ATSS assigner)
+// and roi_targets.hip (proposal-target layer).
 // Restates cpd/ops/iou3d_nms/src/iou3d_nms_kernel.cu:35-234 with the reference's fp32 operation order (edge x edge crossings
 // i=0..3 x j=0..3, corners interleaved b-in-a / a-in-b, centroid, bubble sort by atan2, shoelace fan), so degenerate cases
 // (MARGIN corners, parallel edges) agree. __host__ __device__: boxes_iou_bev_cpu (iou3d_cpu.cpp:232-252) runs the same code.
@@ -121,6 +122,22 @@ __host__ __device__ inline float box_overlap_g(const BoxG &A, const BoxG &B) {
         area += ux * vy - uy * vx;
     }
     return fabsf(area) / 2.0f;
+}
+
+// boxes_iou3d_gpu, iou3d_nms_utils.py:76-98: the one 3-D IoU expression of this library (iou3d_nms.hip's pairwise_kernel<MODE_IOU3D> and
+// recall_kernel and roi_targets.hip's classify kernel all call it, so a maximum taken by any of them is the same float). Its own
+// operations are kept from contracting, one rounding each -- what the pairwise kernel has always computed: left to the compiler,
+// whether `va + vb - o3` becomes FMAs depends on the caller's loop (in the classify kernel it did, and the overlap came out an ulp
+// or two away from cpd_boxes_iou3d's). box_overlap_g, inlined here, keeps the translation unit's setting.
+__device__ __forceinline__ float iou3d_g(const BoxG &A, const BoxG &B) {
+#pragma clang fp contract(off)
+    const float amax = A.b[2] + A.b[5] / 2, amin = A.b[2] - A.b[5] / 2;
+    const float bmax = B.b[2] + B.b[5] / 2, bmin = B.b[2] - B.b[5] / 2;
+    float oh = fminf(amax, bmax) - fmaxf(amin, bmin);
+    oh = oh < 0.f ? 0.f : oh;
+    const float o3 = box_overlap_g(A, B) * oh;
+    const float va = A.b[3] * A.b[4] * A.b[5], vb = B.b[3] * B.b[4] * B.b[5];
+    return o3 / fmaxf(va + vb - o3, 1e-6f);
 }
 
 __host__ __device__ __forceinline__ float iou_bev_g(const BoxG &A, const BoxG &B) {

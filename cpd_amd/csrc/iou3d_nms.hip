@@ -24,18 +24,6 @@ namespace {
 
 enum { MODE_OVERLAP = 0, MODE_IOU_BEV = 1, MODE_IOU3D = 2 };
 
-// boxes_iou3d_gpu, iou3d_nms_utils.py:76-98: the one 3-D IoU expression of this library (pairwise_kernel<MODE_IOU3D> and
-// recall_kernel both call it, so a column maximum taken by either is the same float)
-__device__ __forceinline__ float iou3d_g(const BoxG &A, const BoxG &B) {
-    const float amax = A.b[2] + A.b[5] / 2, amin = A.b[2] - A.b[5] / 2;
-    const float bmax = B.b[2] + B.b[5] / 2, bmin = B.b[2] - B.b[5] / 2;
-    float oh = fminf(amax, bmax) - fmaxf(amin, bmin);
-    oh = oh < 0.f ? 0.f : oh;
-    const float o3 = box_overlap_g(A, B) * oh;
-    const float va = A.b[3] * A.b[4] * A.b[5], vb = B.b[3] * B.b[4] * B.b[5];
-    return o3 / fmaxf(va + vb - o3, 1e-6f);
-}
-
 // Pairwise matrices: lane = column box (b side, kept in registers), each wave walks 16 rows.
 template <int MODE>
 __global__ void __launch_bounds__(256) pairwise_kernel(const float *__restrict__ a, int n, const float *__restrict__ b,

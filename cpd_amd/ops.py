@@ -820,6 +820,102 @@ def recall_record(pred, pred_start, pred_count, gt, thresh, counters, rois=None,
           "cpd_recall_record")
 
 
+ROI_SCORE_TYPES = {"cls": 0, "roi_iou": 1, "roi_ioud": 2, "roi_iou_x": 3, "roi_ioud_x": 4}      # CPD_ROI_SCORE_* of include/cpd_hip.h
+ROI_TARGETS_MAX_CLASSES = 8                                                                     # CPD_ROI_TARGETS_MAX_CLASSES
+
+
+def roi_targets_views(workspace, batch, n):
+    """The five [batch, n] pieces of a cpd_roi_targets workspace as views: (max_overlaps f32, assignment i32, (fg, hard, easy) i32
+    index lists, valid up to the pool's count)."""
+    words = batch * n
+    piece = (words * 4 + 255) // 256 * 256
+    cut = [workspace[k * piece:k * piece + words * 4] for k in range(5)]
+    i32 = [c.view(torch.int32).view(batch, n) for c in cut[1:]]
+    return cut[0].view(torch.float32).view(batch, n), i32[0], tuple(i32[1:])
+
+
+def roi_targets_classify(rois, roi_labels, gt_boxes, by_class, fg_thresh, reg_thresh, bg_thresh_lo, workspace=None, counts=None):
+    """cpd_roi_targets_classify: every RoI's best ground truth and the three sampling pools for all frames in one launch, queued on
+    the current stream. rois [B, N, 7] f32, roi_labels [B, N] i64, gt_boxes [B, M, ld >= 7] f32 on the device (the class in the last
+    column). fg_thresh / reg_thresh: host floats (scalar thresholds; fg_thresh = min(REG_FG_THRESH, CLS_FG_THRESH)) or equally long
+    lists of them (the per-class lists of roi_iou_x / roi_ioud_x). -> (counts [B, 4] i32 on the device = fg, hard, easy, kept gt
+    rows; workspace: read it with roi_targets_views)."""
+    _need_cuda(rois, "rois")
+    _need_cuda(gt_boxes, "gt_boxes")
+    assert rois.dim() == 3 and rois.shape[2] == 7 and rois.dtype == torch.float32 and rois.is_contiguous()
+    assert roi_labels.shape == rois.shape[:2] and roi_labels.dtype == torch.int64 and roi_labels.is_contiguous() and roi_labels.is_cuda
+    assert gt_boxes.dim() == 3 and gt_boxes.shape[0] == rois.shape[0] and gt_boxes.dtype == torch.float32 and gt_boxes.is_contiguous()
+    batch, n = int(rois.shape[0]), int(rois.shape[1])
+    lists = isinstance(fg_thresh, (list, tuple))
+    fg, reg = (list(fg_thresh), list(reg_thresh)) if lists else ([fg_thresh], [reg_thresh])
+    assert len(fg) == len(reg)
+    need = int(lib().cpd_roi_targets_workspace_bytes(batch, n))
+    if workspace is None:
+        workspace = torch.empty((max(need, 256),), dtype=torch.uint8, device=rois.device)
+    if counts is None:
+        counts = torch.empty((batch, 4), dtype=torch.int32, device=rois.device)
+    assert workspace.dtype == torch.uint8 and workspace.numel() >= need and counts.dtype == torch.int32 and counts.numel() == 4 * batch
+    check(lib().cpd_roi_targets_classify(ptr(rois), ptr(roi_labels), batch, n, ptr(gt_boxes), int(gt_boxes.shape[1]), int(gt_boxes.shape[2]),
+                                         int(bool(by_class)), farr(fg), farr(reg), len(fg) if lists else 0, float(bg_thresh_lo), ptr(counts),
+                                         ptr(workspace), workspace.numel(), stream()), "cpd_roi_targets_classify")
+    return counts, workspace
+
+
+def roi_targets_gather(rois, roi_labels, roi_scores, gt_boxes, picks, counts, workspace, score_type, reg_fg_thresh, cls_fg_thresh,
+                       cls_bg_thresh, extras=None, hard_sampling=None, direction=None, canonical=True):
+    """cpd_roi_targets_gather: the sampled rows and every target derived from them in one launch, queued on the current stream.
+    picks [B, P, 2] i32 on the device = (pool, position) per slot; counts / workspace: roi_targets_classify's. score_type: a
+    CLS_SCORE_TYPE; the thresholds: host floats, or equally long lists for the _x types. extras: {name: [B, M] f32} gathered
+    through the assignment (at most three). hard_sampling: (HARD_SAMPLING_THRESH list, every list, offset list) or None.
+    direction: (DIRECTION_MIN, DIRECTION_MAX) for the _ioud types.
+    -> dict: rois, roi_labels, roi_scores, gt_iou_of_rois, gt_of_rois_src, gt_of_rois (canonical; absent when not `canonical`),
+    reg_valid_mask, rcnn_cls_labels, additional_data."""
+    _need_cuda(rois, "rois")
+    batch, n = int(rois.shape[0]), int(rois.shape[1])
+    m, ld = int(gt_boxes.shape[1]), int(gt_boxes.shape[2])
+    per = int(picks.shape[1])
+    dev = rois.device
+    assert rois.shape[2] == 7 and rois.dtype == torch.float32 and rois.is_contiguous() and gt_boxes.dtype == torch.float32 and gt_boxes.is_contiguous()
+    assert roi_labels.dtype == torch.int64 and roi_labels.is_contiguous() and roi_scores.dtype == torch.float32 and roi_scores.is_contiguous()
+    assert roi_labels.numel() == batch * n and roi_scores.numel() == batch * n
+    assert picks.is_cuda and picks.dtype == torch.int32 and picks.is_contiguous() and tuple(picks.shape) == (batch, per, 2)
+    assert counts.dtype == torch.int32 and counts.numel() == 4 * batch and workspace.dtype == torch.uint8
+    kind = ROI_SCORE_TYPES[score_type]
+    per_class = kind >= 3
+    as_list = lambda v: [float(x) for x in v] if per_class else [float(v)]
+    reg, fg, bg = as_list(reg_fg_thresh), as_list(cls_fg_thresh), as_list(cls_bg_thresh)
+    assert len(reg) == len(fg) == len(bg) and 1 <= len(reg) <= ROI_TARGETS_MAX_CLASSES
+    inv_span = [1.0 / (f - b) for f, b in zip(fg, bg)]               # torch's reciprocal of a host divisor: in double; farr casts it
+    hard = (None, None, None)
+    if hard_sampling is not None:
+        assert per_class and all(len(v) >= len(reg) for v in hard_sampling)
+        hard = (farr(hard_sampling[0][:len(reg)]), iarr(hard_sampling[1][:len(reg)]), iarr(hard_sampling[2][:len(reg)]))
+    dirs = None
+    if kind in (2, 4):
+        dirs = farr([direction[0], direction[1], 1.0 / (direction[1] - direction[0])])
+    extras = extras or {}
+    assert len(extras) <= 3
+    e_in, e_out = (ctypes.c_void_p * 3)(), (ctypes.c_void_p * 3)()
+    add = {}
+    for k, (name, t) in enumerate(extras.items()):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (batch, m), name
+        add[name] = torch.empty((batch, per), dtype=torch.float32, device=dev)
+        e_in[k], e_out[k] = t.data_ptr(), add[name].data_ptr()
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
+    out = {"rois": f32(batch, per, 7), "roi_labels": i64(batch, per), "roi_scores": f32(batch, per), "gt_iou_of_rois": f32(batch, per),
+           "gt_of_rois_src": f32(batch, per, ld), "reg_valid_mask": i64(batch, per),
+           "rcnn_cls_labels": i64(batch, per) if kind == 0 else f32(batch, per), "additional_data": add}
+    if canonical:
+        out["gt_of_rois"] = f32(batch, per, ld)
+    check(lib().cpd_roi_targets_gather(ptr(rois), ptr(roi_labels), ptr(roi_scores), batch, n, ptr(gt_boxes), m, ld, e_in, ptr(picks), per,
+                                       ptr(counts), ptr(workspace), workspace.numel(), kind, len(reg), farr(reg), farr(fg), farr(bg), farr(inv_span),
+                                       hard[0], hard[1], hard[2], dirs, ptr(out["rois"]), ptr(out["roi_labels"]), ptr(out["roi_scores"]),
+                                       ptr(out["gt_iou_of_rois"]), ptr(out["gt_of_rois_src"]), ptr(out.get("gt_of_rois")),
+                                       ptr(out["reg_valid_mask"]), ptr(out["rcnn_cls_labels"]), e_out, stream()), "cpd_roi_targets_gather")
+    return out
+
+
 def wbf_workspace_bytes(n):
     return int(lib().cpd_wbf_workspace_bytes(int(n)))
 

@@ -12,9 +12,13 @@ the differentiable grouping (`cpd_voxel_query*`, `cpd_group_points`, `cpd_group_
 BatchNorm with batch statistics and the loss formulas are torch ops on the device, as they are in the reference (with
 `VoxelRCNNProtoHead.fused_loss` the loss and its gradient are one `cpd_rcnn_proto_loss` launch instead). The branches
 built are the ones the shipped config selects (voxel_rcnn_cproto_center.yaml: CLS_SCORE_TYPE roi_iou or cls, scalar thresholds,
-BinaryCrossEntropy, smooth-l1, corner regularisation); the per-class threshold variants (roi_iou_x / roi_ioud*) raise.
+BinaryCrossEntropy, smooth-l1, corner regularisation); the target layer serves all five CLS_SCORE_TYPEs (cls, roi_iou, roi_ioud and
+the per-class threshold lists of roi_iou_x / roi_ioud_x, with ENABLE_HARD_SAMPLING).
 The sampler draws its random numbers with the same calls in the same order as the reference (np.random.permutation / rand,
 torch.randint on the CPU generator), so equal seeds give equal samples.
+`ProposalTargetLayer.fused` (default False; set_fused_targets flips it on a whole model): assign_targets runs as two launches
+(`cpd_roi_targets_classify`, `cpd_roi_targets_gather`) around one read-back of the pools' lengths, the host's draws
+(plan_target_draws) and one upload of the pick table, instead of the per-frame / per-class loops with their host stalls.
 """
 import math
 
@@ -315,11 +319,75 @@ def set_fused_loss(model, on=True):
     return n
 
 
+def set_fused_targets(model, on=True):
+    """Flip `fused` on every ProposalTargetLayer of `model` (VoxelRCNNProtoHead and roi_pool.VoxelRCNNHead share the layer); returns
+    how many there were."""
+    n = 0
+    for mod in model.modules():
+        if isinstance(mod, ProposalTargetLayer):
+            mod.fused = bool(on)
+            n += 1
+    return n
+
+
 # ------------------------------------------------------------------------------------------------ proposal target layer
+POOL_FG, POOL_HARD, POOL_EASY = 0, 1, 2                            # the pools of cpd_roi_targets_classify, in its order
+
+
+def plan_target_draws(counts, cfg):
+    """The random draws of ProposalTargetLayer for a whole batch, from the pools' lengths alone. counts: per frame (n_fg, n_hard,
+    n_easy[, ...]) -- a frame's draws depend on nothing else, so walking the frames in order makes the calls subsample_rois /
+    sample_bg_inds make, in their order: np.random.permutation(n_fg), the torch.randint calls (the zero-size ones too), or
+    np.floor(np.random.rand(P) * n_fg) when there is no background; after all frames the np.random.randint of ENABLE_HARD_SAMPLING
+    (roi_iou_x / roi_ioud_x: one per class). A frame with neither pool raises NotImplementedError, at that frame.
+    -> (picks [B, ROI_PER_IMAGE, 2] int32 = (pool, position in the pool) per sampled slot, hard_offsets: a list per class or None)."""
+    per_image = int(_cfg(cfg, "ROI_PER_IMAGE"))
+    fg_per_image = int(np.round(_cfg(cfg, "FG_RATIO") * per_image))
+    hard_ratio = _cfg(cfg, "HARD_BG_RATIO")
+    picks = np.zeros((len(counts), per_image, 2), np.int32)
+
+    def draw(k, high):
+        return torch.randint(low=0, high=high, size=(k,)).numpy()
+
+    def background(n_hard, n_easy, num):
+        if n_hard > 0 and n_easy > 0:
+            k = min(int(num * hard_ratio), n_hard)
+            h, e = draw(k, n_hard), draw(num - k, n_easy)
+            return np.concatenate([np.full(k, POOL_HARD), np.full(num - k, POOL_EASY)]), np.concatenate([h, e])
+        if n_hard > 0:
+            return np.full(num, POOL_HARD), draw(num, n_hard)
+        if n_easy > 0:
+            return np.full(num, POOL_EASY), draw(num, n_easy)
+        raise NotImplementedError
+    for i, row in enumerate(counts):
+        n_fg, n_hard, n_easy = int(row[0]), int(row[1]), int(row[2])
+        if n_fg > 0 and n_hard + n_easy > 0:
+            k = min(fg_per_image, n_fg)
+            fg = np.random.permutation(n_fg)[:k]
+            pool, pos = background(n_hard, n_easy, per_image - k)
+            pool, pos = np.concatenate([np.full(k, POOL_FG), pool]), np.concatenate([fg, pos])
+        elif n_fg > 0:
+            pool, pos = np.full(per_image, POOL_FG), np.floor(np.random.rand(per_image) * n_fg)
+        elif n_hard + n_easy > 0:
+            pool, pos = background(n_hard, n_easy, per_image)
+        else:
+            raise NotImplementedError("no foreground and no background RoIs in frame %d" % i)
+        picks[i, :, 0], picks[i, :, 1] = pool, pos
+    offsets = None
+    if _cfg(cfg, "CLS_SCORE_TYPE") in ("roi_iou_x", "roi_ioud_x") and _cfg(cfg, "ENABLE_HARD_SAMPLING", False):
+        offsets = [int(np.random.randint(0, int(1 / _cfg(cfg, "HARD_SAMPLING_RATIO")[c]))) for c in range(len(_cfg(cfg, "REG_FG_THRESH")))]
+    return picks, offsets
+
+
 class ProposalTargetLayer(nn.Module):
+    """`fused` (default False; set_fused_targets flips it on a whole model): with device tensors and 7-column RoIs the layer runs as
+    cpd_roi_targets_classify -> one read-back -> plan_target_draws -> one upload -> cpd_roi_targets_gather; anything else takes the
+    torch path below. Same outputs, same samples under equal seeds."""
+
     def __init__(self, roi_sampler_cfg):
         super().__init__()
         self.cfg = roi_sampler_cfg
+        self.fused = False
 
     def g(self, key, default=None):
         return _cfg(self.cfg, key, default)
@@ -421,8 +489,59 @@ class ProposalTargetLayer(nn.Module):
                 extra[key][i] = batch_dict[key][i][:k + 1][assign[sel]]
         return out_rois, out_gt, out_iou, out_scores, out_labels, extra
 
+    def fused_ok(self, batch_dict, ind=""):
+        """Whether the device path serves this batch: device float32 tensors, 7-column RoIs, int64 labels, a known CLS_SCORE_TYPE,
+        threshold lists of one length within the kernels' class limit."""
+        if not self.fused:
+            return False
+        rois, gt = batch_dict["rois"], batch_dict["gt_boxes" + ind]
+        kind = self.g("CLS_SCORE_TYPE")
+        if not (rois.is_cuda and gt.is_cuda and rois.dim() == 3 and rois.shape[-1] == 7 and rois.shape[1] > 0 and gt.dim() == 3 and gt.shape[1] > 0
+                and gt.shape[-1] >= 7 and rois.dtype == gt.dtype == batch_dict["roi_scores"].dtype == torch.float32
+                and batch_dict["roi_labels"].dtype == torch.int64 and kind in ops.ROI_SCORE_TYPES):
+            return False
+        if any(batch_dict[k].dtype != torch.float32 or tuple(batch_dict[k].shape) != tuple(gt.shape[:2])
+               for k in ("css_score", "outline_cls_mask", "outline_reg_mask") if k in batch_dict):
+            return False
+        if kind in ("roi_iou_x", "roi_ioud_x"):
+            n = [len(self.g(k)) for k in ("REG_FG_THRESH", "CLS_FG_THRESH", "CLS_BG_THRESH")]
+            return n[0] == n[1] == n[2] and 1 <= n[0] <= ops.ROI_TARGETS_MAX_CLASSES
+        return True
+
+    @torch.no_grad()
+    def forward_fused(self, batch_dict, ind="", canonical=False):
+        """forward (and, with `canonical`, assign_targets' transformation: `gt_of_rois` canonical, `gt_of_rois_src` the sampled rows)
+        in two launches; see the class."""
+        b = batch_dict["batch_size"]
+        rois, gt = batch_dict["rois"][:b].contiguous(), batch_dict["gt_boxes" + ind][:b].contiguous()
+        labels, scores = batch_dict["roi_labels"][:b].contiguous(), batch_dict["roi_scores"][:b].contiguous()
+        kind = self.g("CLS_SCORE_TYPE")
+        per_class = kind in ("roi_iou_x", "roi_ioud_x")
+        reg_t, cls_t = self.g("REG_FG_THRESH"), self.g("CLS_FG_THRESH")
+        fg_t = [min(r, c) for r, c in zip(reg_t, cls_t)] if per_class else min(reg_t, cls_t)
+        counts, ws = ops.roi_targets_classify(rois, labels, gt, self.g("SAMPLE_ROI_BY_EACH_CLASS", False), fg_t, list(reg_t) if per_class else reg_t,
+                                              self.g("CLS_BG_THRESH_LO"))
+        picks, offsets = plan_target_draws(counts.cpu().numpy(), self.cfg)            # the one read-back
+        picks = torch.from_numpy(picks).to(rois.device)                               # the one upload
+        hard = None
+        if offsets is not None:
+            hard = (list(self.g("HARD_SAMPLING_THRESH")), [int(1 / r) for r in self.g("HARD_SAMPLING_RATIO")], offsets)
+        extras = {k: batch_dict[k][:b].contiguous() for k in ("css_score", "outline_cls_mask", "outline_reg_mask") if k in batch_dict}
+        direction = (self.g("DIRECTION_MIN"), self.g("DIRECTION_MAX")) if kind in ("roi_ioud", "roi_ioud_x") else None
+        t = ops.roi_targets_gather(rois, labels, scores, gt, picks, counts, ws, kind, reg_t, cls_t, self.g("CLS_BG_THRESH"), extras=extras,
+                                   hard_sampling=hard, direction=direction, canonical=canonical)
+        if not canonical:
+            t["gt_of_rois"] = t.pop("gt_of_rois_src")
+        return t
+
     @torch.no_grad()
     def forward(self, batch_dict, ind=""):
+        if self.fused_ok(batch_dict, ind):
+            return self.forward_fused(batch_dict, ind)
+        return self.forward_torch(batch_dict, ind)
+
+    @torch.no_grad()
+    def forward_torch(self, batch_dict, ind=""):
         """l.32-196: CLS_SCORE_TYPE cls / roi_iou / roi_ioud (scalar thresholds) and roi_iou_x / roi_ioud_x (per-class threshold lists
         picked by the class of the RoI's assigned ground truth, l.57-80, 128-184; ENABLE_HARD_SAMPLING draws np.random.randint once per
         class, after the sampling's own draws, and -- as the reference does -- switches whole BATCH rows on: `mask_prob[ints]` indexes
@@ -487,6 +606,8 @@ def assign_targets(target_layer, batch_dict, ind=""):
     """RoIHeadTemplate.assign_targets (roi_head_template.py:116-146): sampling, then the ground truth of every RoI expressed in
     the RoI's canonical frame (centre at the origin, heading zero, flipped when it points the other way)."""
     b = batch_dict["batch_size"]
+    if target_layer.fused_ok(batch_dict, ind):
+        return target_layer.forward_fused(batch_dict, ind, canonical=True)
     with torch.no_grad():
         t = target_layer(batch_dict, ind)
     rois, gt = t["rois"], t["gt_of_rois"]

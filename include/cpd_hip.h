@@ -766,6 +766,59 @@ int cpd_rcnn_proto_loss(const float *cls0, const float *reg0, const float *feat0
                         const float *css_score, int n, const float code_weights[7], float cls_weight, float reg_weight,
                         float corner_weight, float proto_weight, float ramp_weight, int corner_regularization, float *d_cls0,
                         float *d_reg0, float *d_feat0, float *d_cls1, float *d_reg1, float *losses, cpd_stream_t stream);
+/* The RoI head's proposal-target layer on the device: ProposalTargetLayer (cpd/models/roi_heads/target_assigner/
+ * proposal_target_layer.py:32-427: forward, sample_rois_for_rcnn, subsample_rois, get_max_iou_with_same_class) and the canonical
+ * transformation of RoIHeadTemplate.assign_targets (cpd/models/roi_heads/roi_head_template.py:116-146) in TWO launches for a whole
+ * batch, whatever the batch size and class count. The random numbers stay with the caller: cpd_roi_targets_classify, one read-back of
+ * `counts`, the caller's draws (they depend on the counts only), one upload of `picks`, cpd_roi_targets_gather.
+ * rois [batch][n][7] f32 (zero padding rows take part, as in the reference), roi_labels [batch][n] i64, roi_scores [batch][n] f32,
+ * gt_boxes [batch][m][gt_ld] f32 (gt_ld >= 7; columns 0:7 the box, the LAST column the class), n >= 1, m >= 1, batch <= 65535.
+ *
+ * cpd_roi_targets_classify. A frame's ground truth is rows 0 .. k, k the last row whose fp32 sum over all gt_ld columns is not zero
+ * and never below 0 (l.221-225; cpd_recall_record's rule: zero rows before row k stay, an all-zero block keeps row 0). Every RoI gets
+ * its largest cpd_boxes_iou3d value (the same expression, the same bits) over the kept rows -- by_class != 0
+ * (SAMPLE_ROI_BY_EACH_CLASS): over the kept rows whose class, truncated to an integer, equals the RoI's label, overlap 0 and row 0 when
+ * there is none -- and the LOWEST row that attains it (torch.max(dim=1) on the device). Three pools follow, with thresholds compared
+ * as fp32: fg = overlap >= fg_thresh, hard = bg_thresh_lo <= overlap < reg_thresh, easy = overlap < bg_thresh_lo; a RoI may be in
+ * fg and hard at once. n_thresh == 0: scalar thresholds fg_thresh[0] (= min(REG_FG_THRESH, CLS_FG_THRESH)) and reg_thresh[0];
+ * n_thresh = 1 .. CPD_ROI_TARGETS_MAX_CLASSES: per-class lists (roi_iou_x / roi_ioud_x, l.300-325), entry c serving the RoIs whose
+ * assigned row has class c + 1, the others in neither fg nor hard. Both are HOST arrays.
+ * Outputs: counts [batch][4] i32 = the lengths of fg, hard, easy and the kept row count; and in the workspace, five pieces of
+ * cpd_roi_targets_workspace_bytes(batch, n) / 5 bytes each, every one a [batch][n] array: max_overlaps f32, assignment i32, then the
+ * fg, hard and easy pools as ascending RoI indices (nonzero() order; the entries past a pool's length are not written).
+ * One workgroup per frame, stable compaction by ballot and prefix: two calls agree bit for bit.
+ *
+ * cpd_roi_targets_gather reads that workspace and `counts` (device) and picks [batch][per_image][2] i32 = (pool 0 / 1 / 2, position in
+ * the pool) per sampled slot (a pick outside its pool reads RoI 0). It writes, per slot: out_rois [..][7], out_roi_labels i64,
+ * out_roi_scores, out_gt_iou, out_gt_src [..][gt_ld] (the assigned row, all columns), out_gt_canonical [..][gt_ld] (NULL to skip:
+ * the row with its centre moved by the RoI's, turned by -(heading mod 2 pi), the opposite-facing half turn folded and the heading
+ * clamped to +-pi/2, operation for operation in fp32), extras_out[k] [batch][per_image] = extras_in[k] [batch][m] through the
+ * assignment for each non-NULL k (css_score, outline_cls_mask, outline_reg_mask; extras_in may itself be NULL), out_reg_valid i64 and
+ * out_cls_labels (i64 for CPD_ROI_SCORE_CLS, f32 otherwise) for score_type = CLS_SCORE_TYPE (l.57-196). Host arrays of n_cls entries
+ * (1 for the scalar types): reg_fg_thresh, cls_fg_thresh, cls_bg_thresh, cls_inv_span = float(1 / (CLS_FG_THRESH - CLS_BG_THRESH)) with
+ * the difference and the reciprocal formed in double; for the _X types entry c serves assigned class c + 1, and hard_thresh / hard_every / hard_offset (NULL:
+ * ENABLE_HARD_SAMPLING off) switch the batch rows hard_offset[c], + hard_every[c], ... on (hard_every[c] = int(1 /
+ * HARD_SAMPLING_RATIO[c]), hard_offset[c] the caller's draw; the reference indexes dimension 0 of the mask). direction (the _IOUD
+ * types) = DIRECTION_MIN, DIRECTION_MAX, float(1 / (MAX - MIN)). The soft labels are torch's fp32 kernels one rounding at a time (torch
+ * divides a device tensor by a host scalar as a product with the scalar's reciprocal, formed in double and cast to float). */
+#define CPD_ROI_TARGETS_MAX_CLASSES 8
+#define CPD_ROI_SCORE_CLS 0
+#define CPD_ROI_SCORE_ROI_IOU 1
+#define CPD_ROI_SCORE_ROI_IOUD 2
+#define CPD_ROI_SCORE_ROI_IOU_X 3
+#define CPD_ROI_SCORE_ROI_IOUD_X 4
+size_t cpd_roi_targets_workspace_bytes(int batch, int n);
+int cpd_roi_targets_classify(const float *rois, const int64_t *roi_labels, int batch, int n, const float *gt_boxes, int m,
+                             int gt_ld, int by_class, const float *fg_thresh, const float *reg_thresh, int n_thresh,
+                             float bg_thresh_lo, int32_t *counts, void *ws, size_t ws_bytes, cpd_stream_t stream);
+int cpd_roi_targets_gather(const float *rois, const int64_t *roi_labels, const float *roi_scores, int batch, int n,
+                           const float *gt_boxes, int m, int gt_ld, const float *const extras_in[3], const int32_t *picks,
+                           int per_image, const int32_t *counts, const void *ws, size_t ws_bytes, int score_type, int n_cls,
+                           const float *reg_fg_thresh, const float *cls_fg_thresh, const float *cls_bg_thresh,
+                           const float *cls_inv_span, const float *hard_thresh, const int32_t *hard_every,
+                           const int32_t *hard_offset, const float direction[3], float *out_rois, int64_t *out_roi_labels,
+                           float *out_roi_scores, float *out_gt_iou, float *out_gt_src, float *out_gt_canonical,
+                           int64_t *out_reg_valid, void *out_cls_labels, float *const extras_out[3], cpd_stream_t stream);
 /* Adam with decoupled weight decay on a flat buffer (tools/train_utils/optimization/fastai_optim.py:
  * 132-150 true_wd semantics): grad is multiplied first by grad_scale (1/world after all-reduce) and,
  * when grad_scale_dev is not NULL, by the float it points to in device memory (the clip factor of

@@ -4,8 +4,10 @@
   * get_loss + backward + the tb_dict read-back on synthetic targets_dict0 / targets_dict1: VoxelRCNNProtoHead.fused_loss on (one
     `cpd_rcnn_proto_loss` launch) against off (the torch chain with its read-backs);
   * one head training step -- forward (proposal layer, sampling, both pooling branches with fused_train on, FC stacks) + get_loss +
-    backward on synthetic sparse levels and proposals -- with fused_loss off and on, and the same step split into phases by events.
-The two settings are alternated in one process, --pairs times; every figure is the median of event-timed repetitions after warm-up,
+    backward on synthetic sparse levels and proposals -- with fused_loss off and on, and the same step split into phases by events;
+  * with fused_loss on, the head step and its "target sampling" phase with ProposalTargetLayer.fused off (the torch path) and on
+    (cpd_roi_targets_classify / cpd_roi_targets_gather: two launches, one read-back, one upload).
+The two settings of a switch are alternated in one process, --pairs times; every figure is the median of event-timed repetitions after warm-up,
 per pair and over all pairs. Prints one JSON line.  Usage: python tools/proto_head_train_time.py [--pairs 5]"""
 import argparse
 import json
@@ -73,7 +75,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=5, help="how many times the two settings are alternated")
     opt = ap.parse_args()
     from cpd_amd import models, roi_pool
-    from cpd_amd.roi_head_train import VoxelRCNNProtoHead, assign_targets
+    from cpd_amd.roi_head_train import VoxelRCNNProtoHead, assign_targets, set_fused_targets
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0), "pairs": opt.pairs}
     cfg = models.waymo_voxel_rcnn_cfg().ROI_HEAD
@@ -173,6 +175,30 @@ def main():
             runs[flag] += [phases(flag) for _ in range(10)]
     out["head_step_phases_ms"] = {key: {k: float(v) for k, v in zip(names, np.median(np.array(runs[flag]), axis=0))}
                                   for key, flag in (("torch", False), ("fused", True))}
+
+    # the device target layer against the torch path (fused_loss on in both settings)
+    def step_targets(fused_targets):
+        set_fused_targets(head, fused_targets)
+        step(True)
+
+    def sampling(fused_targets):
+        set_fused_targets(head, fused_targets)
+        return phases(True)[1]
+    for flag in (False, True):
+        sampling(flag)
+    per, every = {"torch": [], "fused": []}, {"torch": [], "fused": []}
+    for _ in range(opt.pairs):
+        for key, flag in (("torch", False), ("fused", True)):
+            sampling(flag)
+            t = [sampling(flag) for _ in range(20)]
+            per[key].append(float(np.median(t)))
+            every[key] += t
+    out["fused_targets"] = {
+        "target_sampling": {"torch_ms": float(np.median(every["torch"])), "fused_ms": float(np.median(every["fused"])),
+                            "pairs_torch_ms": per["torch"], "pairs_fused_ms": per["fused"],
+                            "fused_below_torch_in_every_pair": all(f < t for f, t in zip(per["fused"], per["torch"]))},
+        "head_step": alternated(step_targets, opt.pairs, reps=10, warmup=2)}
+    set_fused_targets(head, False)
     print(json.dumps(out))
 
 

@@ -7,7 +7,11 @@
     sparse levels and proposals; the same step split into phases by events (proposal layer, target sampling, pooling forward, FC
     stacks, loss, backward) and its peak allocated memory. --fused-pool turns NeighborVoxelSAModuleMSG.fused_train on
     (roi_pool.set_fused_train): pooling through cpd_voxel_pool_max_train instead of the module sequence.
-Median of cuda-event-timed repetitions after warm-up. Prints one JSON line.  Usage: python tools/rcnn_head_train_time.py [--fused-pool]"""
+  * the head step and its "target sampling" phase with ProposalTargetLayer.fused off (the torch path) and on (cpd_roi_targets_classify /
+    cpd_roi_targets_gather: two launches, one read-back, one upload), alternated in one process --pairs times: per-pair medians and
+    the overall ones.
+Median of cuda-event-timed repetitions after warm-up. Prints one JSON line.
+Usage: python tools/rcnn_head_train_time.py [--fused-pool] [--pairs 5]"""
 import argparse
 import json
 import os
@@ -50,9 +54,10 @@ def loss_rows(n, seed=0):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--fused-pool", action="store_true", help="train the pooling through the fused op (fused_train on every pooling module)")
+    ap.add_argument("--pairs", type=int, default=5, help="how many times the two target-layer settings are alternated")
     opt = ap.parse_args()
     from cpd_amd import models, roi_pool
-    from cpd_amd.roi_head_train import assign_targets
+    from cpd_amd.roi_head_train import assign_targets, set_fused_targets
     from cpd_amd.roi_head_train import rcnn_head_loss, rcnn_head_loss_torch
     torch.cuda.set_device(0)
     out = {"device": torch.cuda.get_device_name(0)}
@@ -157,6 +162,35 @@ def main():
         phases()
     runs = np.array([phases() for _ in range(20)])
     out["head_step_phases_ms"] = {k: float(v) for k, v in zip(names, np.median(runs, axis=0))}
+
+    # the device target layer against the torch path: the settings alternated, the "target sampling" phase and the whole step
+    per_pair = {key: {"target_sampling": [], "head_step": []} for key in ("torch", "fused")}
+    every = {key: {"target_sampling": [], "head_step": []} for key in ("torch", "fused")}
+    for _ in range(opt.pairs):
+        for key, flag in (("torch", False), ("fused", True)):
+            set_fused_targets(head, flag)
+            phases()
+            sampling = [phases()[1] for _ in range(20)]
+            steps = []
+            step()
+            torch.cuda.synchronize()
+            for _ in range(10):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                step()
+                b.record()
+                b.synchronize()
+                steps.append(a.elapsed_time(b))
+            for name, t in (("target_sampling", sampling), ("head_step", steps)):
+                per_pair[key][name].append(float(np.median(t)))
+                every[key][name] += t
+    set_fused_targets(head, False)
+    out["fused_targets"] = {"pairs": opt.pairs}
+    for name in ("target_sampling", "head_step"):
+        out["fused_targets"][name] = {
+            "torch_ms": float(np.median(every["torch"][name])), "fused_ms": float(np.median(every["fused"][name])),
+            "pairs_torch_ms": per_pair["torch"][name], "pairs_fused_ms": per_pair["fused"][name],
+            "fused_below_torch_in_every_pair": all(f < t for f, t in zip(per_pair["fused"][name], per_pair["torch"][name]))}
     print(json.dumps(out))
 
 
