@@ -26,7 +26,7 @@ _D = ctypes.c_double
 _I3 = ctypes.POINTER(ctypes.c_int32)
 _FP = ctypes.POINTER(ctypes.c_float)
 
-# name -> (restype, argtypes): one row per declaration in include/cpd_hip.h
+# name -> (restype, argtypes): one row per declaration in include/cpd_hip.h (tests/test_abi.py checks every row against it)
 SIGNATURES = {
     "cpd_launch_log_enable": (None, [_I]),
     "cpd_launch_log_note": (None, [ctypes.c_char_p]),
@@ -43,8 +43,10 @@ SIGNATURES = {
     "cpd_voxelize": (_I, [_VP, _I, _I, _FP, _FP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_index_bytes": (_SZ, [_I, _I3, _I]),
     "cpd_index_build": (_I, [_VP, _I, _I, _I3, _VP, _SZ, _VP]),
+    "cpd_order_rows_by_taps_workspace_bytes": (_SZ, [_I]),
     "cpd_order_rows_by_taps": (_I, [_VP, _I, _I, _I3, _I3, _VP, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_index_set_order": (_I, [_VP, _VP, _VP]),
+    "cpd_order_rows_bricks_workspace_bytes": (_SZ, [_I]),
     "cpd_order_rows_bricks": (_I, [_VP, _I, _I, _I3, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "cpd_rulebook_chunk_ordered": (_I, [_VP, _VP, _I, _I, _I3, _I3, _I3, _I3, _VP, _I, _VP, _VP, _VP]),
     "cpd_rulebook_plan_bytes": (_SZ, [_I, _I, _I]),

@@ -221,11 +221,23 @@ __global__ void __launch_bounds__(256) atss_finalize_kernel(const float *__restr
     }
 }
 
+struct AtssLayout { size_t colmax, cand_idx, cand_iou, cand_pos, total; };
+AtssLayout atss_layout(int m, int topk) {
+    Carve c;
+    AtssLayout l;
+    l.colmax = c.take((size_t)m * 8);
+    l.cand_idx = c.take((size_t)m * topk * 4);
+    l.cand_iou = c.take((size_t)m * topk * 4);
+    l.cand_pos = c.take((size_t)m * topk * 4);
+    l.total = c.o;
+    return l;
+}
+
 }  // namespace
 
 extern "C" size_t cpd_atss_workspace_bytes(int m, int topk) {
     if (m <= 0 || topk <= 0) return 256;
-    return cpd_align((size_t)m * 8) + 3 * cpd_align((size_t)m * topk * 4);
+    return atss_layout(m, topk).total;
 }
 
 extern "C" int cpd_atss_assign(const float *anchors, int n_anchors, const float *gt_boxes, int gt_ld, int m, int topk,
@@ -235,16 +247,13 @@ extern "C" int cpd_atss_assign(const float *anchors, int n_anchors, const float 
         topk <= 0)
         return CPD_ERR_ARG;
     if (topk > ATSS_MAX_K || topk > n_anchors || (long long)topk * m > ATSS_MAX_CAND) return CPD_ERR_UNSUPPORTED;
-    if (workspace_bytes < cpd_atss_workspace_bytes(m, topk)) return CPD_ERR_WORKSPACE;
+    const AtssLayout l = atss_layout(m, topk);
+    if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     hipStream_t s = cpd_s(stream);
-    char *w = static_cast<char *>(workspace);
-    unsigned long long *colmax = reinterpret_cast<unsigned long long *>(w);
-    w += cpd_align((size_t)m * 8);
-    int32_t *cand_idx = reinterpret_cast<int32_t *>(w);
-    w += cpd_align((size_t)m * topk * 4);
-    float *cand_iou = reinterpret_cast<float *>(w);
-    w += cpd_align((size_t)m * topk * 4);
-    int32_t *cand_pos = reinterpret_cast<int32_t *>(w);
+    unsigned long long *colmax = ws_at<unsigned long long>(workspace, l.colmax);
+    int32_t *cand_idx = ws_at<int32_t>(workspace, l.cand_idx);
+    float *cand_iou = ws_at<float>(workspace, l.cand_iou);
+    int32_t *cand_pos = ws_at<int32_t>(workspace, l.cand_pos);
     CPD_HIP_TRY(hipMemsetAsync(labels, 0, (size_t)n_anchors * 4, s));
     CPD_HIP_TRY(hipMemsetAsync(reg_targets, 0, (size_t)n_anchors * 7 * 4, s));
     CPD_HIP_TRY(hipMemsetAsync(reg_weights, 0, (size_t)n_anchors * 4, s));

@@ -296,9 +296,10 @@ struct FilterLayout {
 };
 FilterLayout filter_layout(int n_segments) {
     FilterLayout L;
-    L.thr = 0;
-    L.counts = cpd_align((size_t)n_segments * 4);
-    L.total = L.counts + cpd_align((size_t)n_segments * 4);
+    Carve c;
+    L.thr = c.take((size_t)n_segments * 4);
+    L.counts = c.take((size_t)n_segments * 4);
+    L.total = c.o;
     return L;
 }
 
@@ -408,14 +409,18 @@ __global__ void __launch_bounds__(CP_THREADS) cp_best_fill_kernel(ScoreArgs a) {
     });
 }
 
+// per_seg: one word per segment that the size query has always counted; no kernel touches it. The launcher clears the two
+// per-row pieces in front of it, [0, per_seg).
 struct ScoreLayout {
-    size_t csize, czmax, total;
+    size_t csize, czmax, per_seg, total;
 };
-ScoreLayout score_layout(long long n_rows) {
+ScoreLayout score_layout(int n_segments, long long n_rows) {
     ScoreLayout L;
-    L.csize = 0;
-    L.czmax = cpd_align((size_t)n_rows * 4);
-    L.total = L.czmax + cpd_align((size_t)n_rows * 4);
+    Carve c;
+    L.csize = c.take((size_t)n_rows * 4);
+    L.czmax = c.take((size_t)n_rows * 4);
+    L.per_seg = c.take((size_t)n_segments * 4);
+    L.total = c.o;
     return L;
 }
 
@@ -498,7 +503,7 @@ int cpd_cproto_filter(const void *rows, int is_half, const int32_t *seg_off, con
 
 size_t cpd_cproto_score_workspace_bytes(int n_segments, int n_rows) {
     if (n_segments < 0 || n_rows < 0) return 0;
-    return score_layout(n_rows > 0 ? n_rows : 1).total + cpd_align((size_t)(n_segments > 0 ? n_segments : 1) * 4);
+    return score_layout(n_segments > 0 ? n_segments : 1, n_rows > 0 ? n_rows : 1).total;
 }
 
 int cpd_cproto_score(const float *ng_xyz, const int32_t *ng_src, const int32_t *filt_off, const int32_t *ng_count,
@@ -515,8 +520,8 @@ int cpd_cproto_score(const float *ng_xyz, const int32_t *ng_src, const int32_t *
                            !best_count))
         return CPD_ERR_ARG;
     if (n_rows > 0 && (!ng_xyz || !ng_src || !labels || !filt_src || !out_xyz || !out_src)) return CPD_ERR_ARG;
-    const ScoreLayout L = score_layout(n_rows > 0 ? n_rows : 1);
-    if (!workspace || workspace_bytes < cpd_cproto_score_workspace_bytes(n_segments, n_rows)) return CPD_ERR_WORKSPACE;
+    const ScoreLayout L = score_layout(n_segments > 0 ? n_segments : 1, n_rows > 0 ? n_rows : 1);
+    if (!workspace || workspace_bytes < L.total) return CPD_ERR_WORKSPACE;
     hipStream_t st = cpd_s(stream);
     ScoreArgs a;
     a.xyz = ng_xyz, a.ng_src = ng_src, a.off = filt_off, a.count = ng_count, a.labels = labels, a.n_clusters = n_clusters;
@@ -526,7 +531,7 @@ int cpd_cproto_score(const float *ng_xyz, const int32_t *ng_src, const int32_t *
     a.csize = ws_at<int32_t>(workspace, L.csize), a.czmax = ws_at<uint32_t>(workspace, L.czmax);
     a.occ = occ, a.best_label = best_label, a.best_count = best_count, a.out_off = out_off, a.out_xyz = out_xyz;
     a.out_src = out_src;
-    CPD_HIP_TRY(hipMemsetAsync(workspace, 0, L.total, st));   // sizes 0, max z keys below every float
+    CPD_HIP_TRY(hipMemsetAsync(workspace, 0, L.per_seg, st));   // sizes 0, max z keys below every float
     if (n_segments > 0 && n_rows > 0) cp_cluster_stats_kernel<<<cpd_div_up(n_rows, CP_THREADS), CP_THREADS, 0, st>>>(a);
     if (n_segments > 0) cp_best_occ_kernel<<<n_segments, CP_THREADS, 0, st>>>(a);
     cp_offsets_kernel<<<1, 1024, 0, st>>>(best_count, n_segments, out_off, -1);

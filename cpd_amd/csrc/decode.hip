@@ -485,11 +485,23 @@ static int check_topk_shape(int batch, int num_class, int h, int w, int k) {
     return CPD_OK;
 }
 
+// the per-class top-K candidates of cpd_center_decode and cpd_center_peaks: [batch][num_class][k] scores, then their pixels
+struct TopkLayout { size_t score, index, total; };
+TopkLayout topk_layout(int batch, int num_class, int k) {
+    const size_t bytes = (size_t)batch * num_class * k * 4;
+    Carve c;
+    TopkLayout l;
+    l.score = c.take(bytes);
+    l.index = c.take(bytes);
+    l.total = c.o;
+    return l;
+}
+
 }  // namespace
 
 extern "C" size_t cpd_center_decode_workspace_bytes(int batch, int num_class, int hw, int k) {
     if (batch <= 0 || num_class <= 0 || hw <= 0 || k <= 0) return 0;
-    return cpd_align((size_t)batch * num_class * k * 4) * 2;
+    return topk_layout(batch, num_class, k).total;
 }
 
 extern "C" int cpd_center_decode(const float *hm, const float *center, const float *center_z, const float *dim,
@@ -504,10 +516,11 @@ extern "C" int cpd_center_decode(const float *hm, const float *center, const flo
         return CPD_ERR_ARG;
     if (const int rc = check_topk_shape(batch, num_class, h, w, k)) return rc;
     const long long hw = (long long)h * w;
-    if (workspace_bytes < cpd_center_decode_workspace_bytes(batch, num_class, (int)hw, k)) return CPD_ERR_WORKSPACE;
+    const TopkLayout l = topk_layout(batch, num_class, k);
+    if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     hipStream_t s = cpd_s(stream);
-    float *s1 = (float *)workspace;
-    int32_t *i1 = (int32_t *)((char *)workspace + cpd_align((size_t)batch * num_class * k * 4));
+    float *s1 = ws_at<float>(workspace, l.score);
+    int32_t *i1 = ws_at<int32_t>(workspace, l.index);
     topk_class_kernel<<<dim3(num_class, batch), 1024, 0, s>>>(MapView{hm, pix_stride, ch_stride}, sample_stride, num_class,
                                                               (int)hw, k, s1, i1);
     DecodeParams q;
@@ -532,10 +545,11 @@ extern "C" int cpd_center_peaks(const float *hm, int batch, long long sample_str
     if (!hm || !peak_score || !peak_cand || !peak_ind || !workspace) return CPD_ERR_ARG;
     if (const int rc = check_topk_shape(batch, num_class, h, w, k)) return rc;
     const int hw = h * w;
-    if (workspace_bytes < cpd_center_peaks_workspace_bytes(batch, num_class, hw, k)) return CPD_ERR_WORKSPACE;
+    const TopkLayout l = topk_layout(batch, num_class, k);
+    if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     hipStream_t s = cpd_s(stream);
-    float *s1 = (float *)workspace;
-    int32_t *i1 = (int32_t *)((char *)workspace + cpd_align((size_t)batch * num_class * k * 4));
+    float *s1 = ws_at<float>(workspace, l.score);
+    int32_t *i1 = ws_at<int32_t>(workspace, l.index);
     topk_class_kernel<<<dim3(num_class, batch), 1024, 0, s>>>(MapView{hm, pix_stride, ch_stride}, sample_stride, num_class, hw, k, s1, i1);
     peaks_kernel<<<batch, 1024, 0, s>>>(num_class, k, s1, i1, peak_score, peak_cand, peak_ind);
     return cpd_check_launch();

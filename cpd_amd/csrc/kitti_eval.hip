@@ -458,10 +458,23 @@ extern "C" int cpd_kitti_overlaps(int metric, int criterion, const void *dt_boxe
     return cpd_check_launch();
 }
 
+// The PR pass keeps per (sweep, threshold, frame) row three counts and one similarity sum, then one `assigned` byte per
+// (sweep, detection). pr_frames = 0 (the score pass, which has no such rows) leaves `assigned` alone, at offset 0.
+struct KeLayout { size_t counts, sims, assigned, total; };
+static KeLayout ke_layout(int n_sweeps, int pr_frames, int total_dt) {
+    const size_t rows = (size_t)n_sweeps * KE_MAX_THR * pr_frames;
+    Carve c;
+    KeLayout l;
+    l.counts = c.take(rows * 3 * sizeof(int32_t));
+    l.sims = c.take(rows * sizeof(double));
+    l.assigned = c.take((size_t)n_sweeps * total_dt);
+    l.total = c.o;
+    return l;
+}
+
 extern "C" size_t cpd_kitti_match_workspace_bytes(int n_sweeps, int n_frames, int total_dt) {
     if (n_sweeps <= 0 || n_frames <= 0 || total_dt < 0) return 0;
-    const size_t rows = (size_t)n_sweeps * KE_MAX_THR * n_frames;
-    return cpd_align(rows * 3 * sizeof(int32_t)) + cpd_align(rows * sizeof(double)) + cpd_align((size_t)n_sweeps * total_dt);
+    return ke_layout(n_sweeps, n_frames, total_dt).total;
 }
 
 extern "C" int cpd_kitti_match_scores(const double *overlaps, const int64_t *pair_off, const int32_t *dt_off, const int32_t *gt_off,
@@ -474,9 +487,9 @@ extern "C" int cpd_kitti_match_scores(const double *overlaps, const int64_t *pai
                                  sweep_min_overlap, n_sweeps, total_gt, total_dt);
     if (rc != CPD_OK) return rc;
     if (total_gt > 0 && (!scores || !matched)) return CPD_ERR_ARG;
-    const size_t need = cpd_align((size_t)n_sweeps * total_dt);
-    if (need > 0 && (!workspace || workspace_bytes < need)) return CPD_ERR_WORKSPACE;
-    a.assigned = static_cast<uint8_t *>(workspace);
+    const KeLayout l = ke_layout(n_sweeps, 0, total_dt);
+    if (l.total > 0 && (!workspace || workspace_bytes < l.total)) return CPD_ERR_WORKSPACE;
+    a.assigned = ws_at<uint8_t>(workspace, l.assigned);
     a.scores = scores;
     a.matched = matched;
     const int64_t lanes = (int64_t)n_sweeps * n_frames;
@@ -499,13 +512,11 @@ extern "C" int cpd_kitti_match_pr(const double *overlaps, const int64_t *pair_of
     if (!dc_off || !thresholds || !n_thresholds || !pr_counts || !pr_sim || metric < 0 || metric > 2) return CPD_ERR_ARG;
     if (total_dt > 0 && (!dt_alpha || !dt_bbox)) return CPD_ERR_ARG;
     if (total_gt > 0 && !gt_alpha) return CPD_ERR_ARG;
-    const size_t need = cpd_kitti_match_workspace_bytes(n_sweeps, n_frames, total_dt);
-    if (!workspace || workspace_bytes < need) return CPD_ERR_WORKSPACE;
-    const size_t rows = (size_t)n_sweeps * KE_MAX_THR * n_frames;
-    char *w = static_cast<char *>(workspace);
-    a.counts = reinterpret_cast<int32_t *>(w);
-    a.sims = reinterpret_cast<double *>(w + cpd_align(rows * 3 * sizeof(int32_t)));
-    a.assigned = reinterpret_cast<uint8_t *>(w + cpd_align(rows * 3 * sizeof(int32_t)) + cpd_align(rows * sizeof(double)));
+    const KeLayout l = ke_layout(n_sweeps, n_frames, total_dt);
+    if (!workspace || workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
+    a.counts = ws_at<int32_t>(workspace, l.counts);
+    a.sims = ws_at<double>(workspace, l.sims);
+    a.assigned = ws_at<uint8_t>(workspace, l.assigned);
     a.dc_off = dc_off; a.dt_alpha = dt_alpha; a.gt_alpha = gt_alpha; a.dt_bbox = dt_bbox; a.dc_bbox = dc_bbox;
     a.thresholds = thresholds; a.n_thresholds = n_thresholds; a.metric = metric; a.compute_aos = compute_aos ? 1 : 0;
     const int64_t lanes = (int64_t)n_sweeps * n_frames;

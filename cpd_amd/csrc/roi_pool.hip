@@ -653,9 +653,21 @@ extern "C" int cpd_nearest_bev_iou(const float *a, int n, const float *b, int m,
     return cpd_check_launch();
 }
 
-extern "C" size_t cpd_anchor_assign_workspace_bytes(int n, int m) {
-    return cpd_align((size_t)(n > 0 ? n : 1) * 8) + cpd_align((size_t)(m > 0 ? m : 1) * 4 + 16);
+// per anchor: best IoU [n] f32, then its GT [n] i32; per GT: best IoU bits [m] i32, then the example count (one memset clears both)
+struct AssignLayout { size_t amax_iou, amax_idx, gmax_bits, n_examples, total; };
+static AssignLayout assign_layout(int n, int m) {
+    const size_t n1 = n > 0 ? n : 1, m1 = m > 0 ? m : 1;
+    Carve c;
+    AssignLayout l;
+    l.amax_iou = c.take(n1 * 8);
+    l.amax_idx = l.amax_iou + n1 * 4;
+    l.gmax_bits = c.take(m1 * 4 + 16);
+    l.n_examples = l.gmax_bits + m1 * 4;
+    l.total = c.o;
+    return l;
 }
+
+extern "C" size_t cpd_anchor_assign_workspace_bytes(int n, int m) { return assign_layout(n, m).total; }
 
 extern "C" int cpd_anchor_assign(const float *anchors, int n, const float *gt, int m, const int32_t *gt_classes, float matched_thr,
                                  float unmatched_thr, int norm_by_num_examples, int32_t *labels, float *bbox_targets,
@@ -663,7 +675,8 @@ extern "C" int cpd_anchor_assign(const float *anchors, int n, const float *gt, i
     if (n < 0 || m < 0 || m > 2048 || !workspace || (n > 0 && (!anchors || !labels || !bbox_targets || !reg_weights || !gt_ious)) ||
         (m > 0 && (!gt || !gt_classes)))
         return CPD_ERR_ARG;
-    if (workspace_bytes < cpd_anchor_assign_workspace_bytes(n, m)) return CPD_ERR_WORKSPACE;
+    const AssignLayout l = assign_layout(n, m);
+    if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     if (n == 0) return CPD_OK;
     hipStream_t s = cpd_s(st);
     if (m == 0) {                                              // no GT of this class: everything is background
@@ -673,10 +686,10 @@ extern "C" int cpd_anchor_assign(const float *anchors, int n, const float *gt, i
         CPD_HIP_TRY(hipMemsetAsync(gt_ious, 0, (size_t)n * 4, s));
         return CPD_OK;
     }
-    float *amax_iou = (float *)workspace;
-    int32_t *amax_idx = (int32_t *)(amax_iou + n);
-    int32_t *gmax_bits = (int32_t *)((char *)workspace + cpd_align((size_t)n * 8));
-    int32_t *n_examples = gmax_bits + m;
+    float *amax_iou = ws_at<float>(workspace, l.amax_iou);
+    int32_t *amax_idx = ws_at<int32_t>(workspace, l.amax_idx);
+    int32_t *gmax_bits = ws_at<int32_t>(workspace, l.gmax_bits);
+    int32_t *n_examples = ws_at<int32_t>(workspace, l.n_examples);
     CPD_HIP_TRY(hipMemsetAsync(gmax_bits, 0, (size_t)(m + 1) * 4, s));
     const int nb = cpd_div_up(n, 256);
     assign_pass1_kernel<<<nb, 256, (size_t)m * 16, s>>>(anchors, n, gt, m, amax_iou, amax_idx, gmax_bits);
@@ -851,9 +864,18 @@ extern "C" int cpd_points_in_boxes_mask(const float *boxes, int k, const float *
     return cpd_check_launch();
 }
 
-extern "C" size_t cpd_crop_boxes_workspace_bytes(int n) {
-    return cpd_align((size_t)(n > 0 ? n : 1)) + cpd_align((size_t)scan_num_blocks(n > 0 ? n : 1) * 4 + 16);
+struct CropLayout { size_t flags, scan, total; };
+static CropLayout crop_layout(int n) {
+    const int n1 = n > 0 ? n : 1;
+    Carve c;
+    CropLayout l;
+    l.flags = c.take((size_t)n1);
+    l.scan = c.take((size_t)scan_num_blocks(n1) * 4 + 16);
+    l.total = c.o;
+    return l;
 }
+
+extern "C" size_t cpd_crop_boxes_workspace_bytes(int n) { return crop_layout(n).total; }
 
 extern "C" int cpd_crop_boxes(const float *points, int n, int c, const float *boxes, const int32_t *discard, int k,
                               float *out_no_object, int32_t *n_no_object, float *out_good_object, int32_t *n_good_object,
@@ -861,14 +883,15 @@ extern "C" int cpd_crop_boxes(const float *points, int n, int c, const float *bo
     if (n < 0 || c < 3 || k < 0 || !n_no_object || !n_good_object || !workspace || (k > 0 && (!boxes || !discard)) ||
         (n > 0 && (!points || !out_no_object || !out_good_object)))
         return CPD_ERR_ARG;
-    if (workspace_bytes < cpd_crop_boxes_workspace_bytes(n)) return CPD_ERR_WORKSPACE;
+    const CropLayout l = crop_layout(n);
+    if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     if (n == 0) {
         CPD_HIP_TRY(hipMemsetAsync(n_no_object, 0, 4, cpd_s(st)));
         CPD_HIP_TRY(hipMemsetAsync(n_good_object, 0, 4, cpd_s(st)));
         return CPD_OK;
     }
-    uint8_t *flags = static_cast<uint8_t *>(workspace);
-    uint32_t *scan_ws = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + cpd_align((size_t)n));
+    uint8_t *flags = ws_at<uint8_t>(workspace, l.flags);
+    uint32_t *scan_ws = ws_at<uint32_t>(workspace, l.scan);
     crop_flags_kernel<<<cpd_div_up(n, 256), 256, 512 * 12 * sizeof(float), cpd_s(st)>>>(points, n, c, boxes, discard, k, flags);
     int rc = cpd_check_launch();
     if (rc != CPD_OK) return rc;

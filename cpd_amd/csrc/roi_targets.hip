@@ -44,14 +44,17 @@ struct RtWs {
     int32_t *lists;              // piece 2, 3, 4 = fg, hard, easy: pool p of frame b at lists + p * stride + b * n
     size_t stride;               // words between two pools' pieces
 };
-static size_t rt_piece_bytes(int batch, int n) { return cpd_align((size_t)batch * n * 4); }
-static RtWs rt_carve(void *ws, int batch, int n) {
-    const size_t piece = rt_piece_bytes(batch, n);
+static RtWs rt_carve(void *ws, int batch, int n, size_t *total) {     // (RtWs is a kernel argument: the total stays out of it)
+    const size_t piece = (size_t)batch * n * 4;
+    Carve c;
     RtWs w;
-    w.overlaps = ws_at<float>(ws, 0);
-    w.assign = ws_at<int32_t>(ws, piece);
-    w.lists = ws_at<int32_t>(ws, 2 * piece);
-    w.stride = piece / 4;
+    w.overlaps = ws_at<float>(ws, c.take(piece));
+    w.assign = ws_at<int32_t>(ws, c.take(piece));
+    const size_t fg = c.take(piece), hard = c.take(piece);
+    c.take(piece);                                                    // easy
+    w.lists = ws_at<int32_t>(ws, fg);
+    w.stride = (hard - fg) / 4;
+    *total = c.o;
     return w;
 }
 
@@ -316,7 +319,9 @@ __global__ void __launch_bounds__(256) roi_targets_gather_kernel(
 
 extern "C" size_t cpd_roi_targets_workspace_bytes(int batch, int n) {
     if (batch <= 0 || n <= 0) return 0;
-    return 5 * rt_piece_bytes(batch, n);
+    size_t total;
+    rt_carve(nullptr, batch, n, &total);
+    return total;
 }
 
 extern "C" int cpd_roi_targets_classify(const float *rois, const int64_t *roi_labels, int batch, int n, const float *gt_boxes, int m, int gt_ld,
@@ -326,7 +331,9 @@ extern "C" int cpd_roi_targets_classify(const float *rois, const int64_t *roi_la
         n_thresh < 0)
         return CPD_ERR_ARG;
     if (n_thresh > RT_MAX_CLASSES) return CPD_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < cpd_roi_targets_workspace_bytes(batch, n)) return CPD_ERR_WORKSPACE;
+    size_t need;
+    const RtWs pieces = rt_carve(ws, batch, n, &need);
+    if (!ws || ws_bytes < need) return CPD_ERR_WORKSPACE;
     RtPools th = {};
     for (int c = 0; c < (n_thresh ? n_thresh : 1); ++c) {
         th.fg[c] = fg_thresh[c];
@@ -335,7 +342,7 @@ extern "C" int cpd_roi_targets_classify(const float *rois, const int64_t *roi_la
     th.lo = bg_thresh_lo;
     th.n = n_thresh;
     roi_targets_classify_kernel<<<batch, RT_THREADS, 0, cpd_s(stream)>>>(rois, reinterpret_cast<const long long *>(roi_labels), n, gt_boxes, m,
-                                                                         gt_ld, by_class != 0, th, rt_carve(ws, batch, n), counts);
+                                                                         gt_ld, by_class != 0, th, pieces, counts);
     cpd_launch_log_note("roi_targets_classify_kernel");
     return cpd_check_launch();
 }
@@ -357,7 +364,9 @@ extern "C" int cpd_roi_targets_gather(const float *rois, const int64_t *roi_labe
     const bool per_class = score_type == CPD_ROI_SCORE_ROI_IOU_X || score_type == CPD_ROI_SCORE_ROI_IOUD_X;
     if ((directed && !direction) || (!per_class && n_cls != 1)) return CPD_ERR_ARG;
     if (n_cls > RT_MAX_CLASSES) return CPD_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < cpd_roi_targets_workspace_bytes(batch, n)) return CPD_ERR_WORKSPACE;
+    size_t need;
+    const RtWs pieces = rt_carve(const_cast<void *>(ws), batch, n, &need);
+    if (!ws || ws_bytes < need) return CPD_ERR_WORKSPACE;
     RtScore sc = {};
     sc.kind = score_type;
     sc.n_cls = n_cls;
@@ -385,7 +394,7 @@ extern "C" int cpd_roi_targets_gather(const float *rois, const int64_t *roi_labe
     dim3 grid(cpd_div_up(per_image, 256), batch);
     roi_targets_gather_kernel<<<grid, 256, 0, cpd_s(stream)>>>(
         rois, reinterpret_cast<const long long *>(roi_labels), roi_scores, n, gt_boxes, m, gt_ld, ex, picks, per_image,
-        rt_carve(const_cast<void *>(ws), batch, n), counts, sc, out_rois, reinterpret_cast<long long *>(out_roi_labels), out_roi_scores,
+        pieces, counts, sc, out_rois, reinterpret_cast<long long *>(out_roi_labels), out_roi_scores,
         out_gt_iou, out_gt_src, out_gt_canonical, reinterpret_cast<long long *>(out_reg_valid), out_cls_labels);
     cpd_launch_log_note("roi_targets_gather_kernel");
     return cpd_check_launch();

@@ -592,6 +592,9 @@ __global__ void index_set_order_kernel(int32_t *flags, const int32_t *rank_to_ro
     flags[0] = rank_to_row ? 2 : 0;
 }
 
+// one piece, a pattern word per row; not rounded up to 256: hosts have always been able to pass exactly 4 n bytes
+extern "C" size_t cpd_order_rows_by_taps_workspace_bytes(int n) { return (size_t)(n > 0 ? n : 1) * 4; }
+
 extern "C" int cpd_order_rows_by_taps(const int32_t *indices, int n, int batch, const int32_t shape_zyx[3], const int32_t ksize[3],
                                       const void *index, int chunk_rows, int32_t *new_to_old, int32_t *old_to_new,
                                       int32_t *indices_out, void *workspace, size_t workspace_bytes, cpd_stream_t stream) {
@@ -601,7 +604,7 @@ extern "C" int cpd_order_rows_by_taps(const int32_t *indices, int n, int batch, 
         if (ksize[d] <= 0 || !(ksize[d] & 1)) return CPD_ERR_ARG;
     if (ksize[0] * ksize[1] * ksize[2] > 32 || ksize[2] > 32) return CPD_ERR_UNSUPPORTED;
     if (chunk_rows != 1024 && chunk_rows != 4096 && chunk_rows != 8192 && chunk_rows != 16384) return CPD_ERR_UNSUPPORTED;
-    if (workspace_bytes < (size_t)(n > 0 ? n : 1) * 4) return CPD_ERR_WORKSPACE;
+    if (workspace_bytes < cpd_order_rows_by_taps_workspace_bytes(n)) return CPD_ERR_WORKSPACE;
     if (n == 0) return CPD_OK;
     hipStream_t s = cpd_s(stream);
     uint32_t *pattern = static_cast<uint32_t *>(workspace);
@@ -623,6 +626,19 @@ extern "C" int cpd_order_rows_by_taps(const int32_t *indices, int n, int batch, 
     return cpd_check_launch();
 }
 
+struct BrickLayout { size_t pattern, pos_to_row, coords, total; };
+static BrickLayout brick_layout(int n) {
+    const size_t n1 = (size_t)(n > 0 ? n : 1);
+    Carve c;
+    BrickLayout l;
+    l.pattern = c.take(n1 * 4);
+    l.pos_to_row = c.take(n1 * 4);
+    l.coords = c.take(n1 * 16);
+    l.total = c.o;
+    return l;
+}
+
+extern "C" size_t cpd_order_rows_bricks_workspace_bytes(int n) { return brick_layout(n).total; }
 
 extern "C" int cpd_order_rows_bricks(const int32_t *indices, int n, int batch, const int32_t shape_zyx[3], const void *index,
                                      int brick_y, int brick_x, int tile_rows, int32_t *new_to_old, int32_t *old_to_new, int32_t *indices_out,
@@ -631,14 +647,13 @@ extern "C" int cpd_order_rows_bricks(const int32_t *indices, int n, int batch, c
     if (!valid_shape(batch, shape_zyx) || n < 0 || !index || brick_y <= 0 || brick_x <= 0 ||
         (n > 0 && (!indices || !new_to_old || !old_to_new || !indices_out || !workspace)))
         return CPD_ERR_ARG;
-    const size_t n1 = (size_t)(n > 0 ? n : 1);
-    if (workspace_bytes < cpd_align(n1 * 4) * 2 + cpd_align(n1 * 16)) return CPD_ERR_WORKSPACE;
+    const BrickLayout l = brick_layout(n);
+    if (workspace_bytes < l.total) return CPD_ERR_WORKSPACE;
     if (n == 0) return CPD_OK;
     hipStream_t s = cpd_s(stream);
-    char *ws = static_cast<char *>(workspace);
-    uint32_t *pattern = reinterpret_cast<uint32_t *>(ws);
-    int32_t *pos_to_row = reinterpret_cast<int32_t *>(ws + cpd_align(n1 * 4));
-    int32_t *coords_b = reinterpret_cast<int32_t *>(ws + 2 * cpd_align(n1 * 4));
+    uint32_t *pattern = ws_at<uint32_t>(workspace, l.pattern);
+    int32_t *pos_to_row = ws_at<int32_t>(workspace, l.pos_to_row);
+    int32_t *coords_b = ws_at<int32_t>(workspace, l.coords);
     IndexView v = index_carve(const_cast<void *>(index), batch, shape_zyx, 1);
     Grid g{batch, shape_zyx[0], shape_zyx[1], shape_zyx[2]};
     // (the index must be the CANONICAL one of `indices`: row = rank)

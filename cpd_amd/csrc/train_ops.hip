@@ -1447,9 +1447,19 @@ extern "C" int cpd_adam_step(float *param, const float *grad, float *exp_avg, fl
 
 // ---- fused CenterHead loss + gradient ----
 static int center_loss_blocks(long long n_rows, int ld) { return (int)cpd_div_up(n_rows * ld, 256); }
+// one piece: three partial sums per block, then the four final sums right behind them
+struct CenterLossLayout { size_t part, fin, total; };
+static CenterLossLayout center_loss_layout(int blocks) {
+    Carve c;
+    CenterLossLayout l;
+    l.part = c.take(((size_t)blocks * 3 + 4) * sizeof(double));
+    l.fin = l.part + (size_t)blocks * 3 * sizeof(double);
+    l.total = c.o;
+    return l;
+}
 extern "C" size_t cpd_center_loss_workspace_bytes(int batch, int hw, int ld) {
     if (batch <= 0 || hw <= 0 || ld <= 0) return 0;
-    return cpd_align(((size_t)center_loss_blocks((long long)batch * hw, ld) * 3 + 4) * sizeof(double));
+    return center_loss_layout(center_loss_blocks((long long)batch * hw, ld)).total;
 }
 extern "C" int cpd_center_loss(const float *rows, int ld, int batch, int hw, int num_classes, int hm_col, const float *heat,
                                const float *target, const int64_t *inds, const int64_t *masks, int k, const float code_weights[8],
@@ -1461,10 +1471,11 @@ extern "C" int cpd_center_loss(const float *rows, int ld, int batch, int hw, int
     const long long n_rows = (long long)batch * hw;
     if (n_rows * ld >= (1ll << 40)) return CPD_ERR_UNSUPPORTED;
     const int blocks = center_loss_blocks(n_rows, ld);
-    if (ws_bytes < ((size_t)blocks * 3 + 4) * sizeof(double)) return CPD_ERR_WORKSPACE;
+    const CenterLossLayout l = center_loss_layout(blocks);
+    if (ws_bytes < l.total) return CPD_ERR_WORKSPACE;
     ClParams p;
     p.rows = rows; p.heat = heat; p.target = target; p.inds = (const long long *)inds; p.masks = (const long long *)masks;
-    p.d_rows = d_rows; p.losses = losses; p.part = (double *)ws; p.fin = (double *)ws + (size_t)blocks * 3;
+    p.d_rows = d_rows; p.losses = losses; p.part = ws_at<double>(ws, l.part); p.fin = ws_at<double>(ws, l.fin);
     p.ld = ld; p.batch = batch; p.hw = hw; p.num_classes = num_classes; p.hm_col = hm_col; p.k = k;
     for (int d = 0; d < 8; ++d) p.cw[d] = code_weights[d];
     p.loc_weight = loc_weight; p.cls_weight = cls_weight;
@@ -1476,10 +1487,19 @@ extern "C" int cpd_center_loss(const float *rows, int ld, int batch, int hw, int
 }
 
 // ---- fused anchor-head loss + gradient ----
+static int anchor_loss_blocks(int batch, int n_anchors) { return (int)cpd_div_up((long long)batch * n_anchors, 256); }
+struct AnchorLossLayout { size_t part, pos, total; };
+static AnchorLossLayout anchor_loss_layout(int batch, int blocks) {
+    Carve c;
+    AnchorLossLayout l;
+    l.part = c.take((size_t)blocks * 3 * sizeof(double));
+    l.pos = c.take((size_t)batch * sizeof(int));
+    l.total = c.o;
+    return l;
+}
 extern "C" size_t cpd_anchor_loss_workspace_bytes(int batch, int n_anchors) {
     if (batch <= 0 || n_anchors <= 0) return 0;
-    const size_t blocks = (size_t)cpd_div_up((long long)batch * n_anchors, 256);
-    return cpd_align(blocks * 3 * sizeof(double)) + cpd_align((size_t)batch * sizeof(int));
+    return anchor_loss_layout(batch, anchor_loss_blocks(batch, n_anchors)).total;
 }
 extern "C" int cpd_anchor_loss(const float *cls_preds, const float *box_preds, const float *dir_preds, const int32_t *labels,
                                const float *reg_targets, const float *anchors, int batch, int n_anchors, int num_class, int num_dir_bins,
@@ -1488,14 +1508,14 @@ extern "C" int cpd_anchor_loss(const float *cls_preds, const float *box_preds, c
     if (!cls_preds || !box_preds || !labels || !reg_targets || !anchors || !code_weights || !d_cls || !d_box || !losses || !ws ||
         batch <= 0 || n_anchors <= 0 || num_class <= 0 || (dir_preds && (!d_dir || num_dir_bins < 2 || num_dir_bins > 16)))
         return CPD_ERR_ARG;
-    if (ws_bytes < cpd_anchor_loss_workspace_bytes(batch, n_anchors)) return CPD_ERR_WORKSPACE;
-    const long long total = (long long)batch * n_anchors;
-    const int blocks = (int)cpd_div_up(total, 256);
+    const int blocks = anchor_loss_blocks(batch, n_anchors);
+    const AnchorLossLayout l = anchor_loss_layout(batch, blocks);
+    if (ws_bytes < l.total) return CPD_ERR_WORKSPACE;
     AlParams p;
     p.cls = cls_preds; p.box = box_preds; p.dir = dir_preds; p.labels = labels; p.reg = reg_targets; p.anchors = anchors;
     p.d_cls = d_cls; p.d_box = d_box; p.d_dir = d_dir; p.losses = losses;
-    p.part = (double *)ws;
-    p.pos = (int *)((char *)ws + cpd_align((size_t)blocks * 3 * sizeof(double)));
+    p.part = ws_at<double>(ws, l.part);
+    p.pos = ws_at<int>(ws, l.pos);
     p.batch = batch; p.n_anchors = n_anchors; p.num_class = num_class; p.num_bins = num_dir_bins;
     p.dir_offset = dir_offset;
     for (int k = 0; k < 7; ++k) p.cw[k] = code_weights[k];

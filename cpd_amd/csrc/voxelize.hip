@@ -73,6 +73,8 @@ struct VoxGeom {
     int32_t g[3];  // z,y,x grid
 };
 
+#define CPD_VOX_MAX_FRAMES 64   // frames of one batched call (below)
+
 struct VoxWs {
     uint64_t *bitmap;   // [words]
     uint32_t *base;     // [words] popcount prefix
@@ -85,11 +87,14 @@ struct VoxWs {
     int32_t *slots;     // [cap*P] kept point indices per voxel (sorted ascending)
     int32_t *counts;    // [cap] points seen per voxel
     int32_t *nocc;      // scalar: occupied cells
+    int32_t *frame_base = nullptr;  // batched entry points only: [CPD_VOX_MAX_FRAMES + 1] first global voxel id per frame,
+    int32_t *out_base = nullptr;    //   [CPD_VOX_MAX_FRAMES + 1] first output row per frame,
+    int32_t *total = nullptr;       //   scalar: voxels over all frames
     long long words;
     size_t bytes;
 };
 
-static VoxWs carve(void *ws, int n, int P, int cap, long long cells) {
+static VoxWs carve(void *ws, int n, int P, int cap, long long cells, bool batch) {
     VoxWs w;
     Carve c;
     w.words = (cells + 63) / 64;
@@ -105,6 +110,12 @@ static VoxWs carve(void *ws, int n, int P, int cap, long long cells) {
     w.slots = ws_at<int32_t>(ws, c.take((size_t)(cap > 0 ? cap : 1) * P * 4));
     w.counts = ws_at<int32_t>(ws, c.take((size_t)(cap > 0 ? cap : 1) * 4));
     w.nocc = ws_at<int32_t>(ws, c.take(4));
+    if (batch) {
+        const size_t per_frame = (CPD_VOX_MAX_FRAMES + 1) * 4, tail = c.take(2 * per_frame + 16);
+        w.frame_base = ws_at<int32_t>(ws, tail);
+        w.out_base = ws_at<int32_t>(ws, tail + per_frame);
+        w.total = ws_at<int32_t>(ws, tail + 2 * per_frame);
+    }
     w.bytes = c.o;
     return w;
 }
@@ -240,7 +251,6 @@ __global__ void __launch_bounds__(256) vox_gather_kernel(const float *__restrict
 // frame's serial order, and a per-frame base turns global ids into the per-frame voxel ids the
 // max_voxels cap applies to. Output rows are the frames' voxels back to back.
 // ------------------------------------------------------------------------------------------
-#define CPD_VOX_MAX_FRAMES 64
 struct FrameOffsets {
     int32_t nf;
     int32_t off[CPD_VOX_MAX_FRAMES + 1];
@@ -620,7 +630,7 @@ extern "C" size_t cpd_voxelize_workspace_bytes(int n_points, int max_points, int
     if (n_points < 0 || max_points <= 0 || max_voxels <= 0) return 0;
     if (vox_geom(vsize_xyz, range_xyz, &g, &cells)) return 0;
     int cap = max_voxels < n_points ? max_voxels : n_points;
-    return carve(nullptr, n_points, max_points, cap, cells).bytes;
+    return carve(nullptr, n_points, max_points, cap, cells, false).bytes;
 }
 
 extern "C" int cpd_voxelize(const float *points, int n_points, int c, const float vsize_xyz[3],
@@ -637,7 +647,7 @@ extern "C" int cpd_voxelize(const float *points, int n_points, int c, const floa
     hipStream_t s = cpd_s(stream);
     const int n = n_points;
     const int cap = max_voxels < n ? max_voxels : n;
-    VoxWs w = carve(workspace, n, max_points, cap, cells);
+    VoxWs w = carve(workspace, n, max_points, cap, cells, false);
     if (workspace_bytes < w.bytes) return CPD_ERR_WORKSPACE;
     if (n == 0) {
         CPD_HIP_TRY(hipMemsetAsync(n_voxels, 0, 4, s));
@@ -680,7 +690,7 @@ extern "C" size_t cpd_voxelize_batch_workspace_bytes(int n_total, int n_frames, 
     if (n_total < 0 || max_points <= 0 || max_voxels <= 0) return 0;
     if (vox_geom(vsize_xyz, range_xyz, &g, &cells)) return 0;
     if (batch_caps(n_total, n_frames, max_voxels, cells, &cap)) return 0;
-    return carve(nullptr, n_total, max_points, cap, (long long)n_frames * cells).bytes + cpd_align(2 * (CPD_VOX_MAX_FRAMES + 1) * 4 + 16);
+    return carve(nullptr, n_total, max_points, cap, (long long)n_frames * cells, true).bytes;
 }
 
 // `index` != NULL: the occupancy bitmap, its popcount prefix and the rank -> row map are built INSIDE that site index (of
@@ -722,8 +732,8 @@ static int voxelize_batch_impl(const float *points, const float *const *frame_po
     hipStream_t s = cpd_s(stream);
     // with an index the bitmap / prefix / scan spine live there: the workspace (sized by cpd_voxelize_batch_workspace_bytes for
     // the plain grid) then carries no bitmap at all
-    VoxWs w = carve(workspace, n, max_points, cap, index ? 0 : (long long)n_frames * cells);
-    if (workspace_bytes < w.bytes + cpd_align(2 * (CPD_VOX_MAX_FRAMES + 1) * 4 + 16)) return CPD_ERR_WORKSPACE;
+    VoxWs w = carve(workspace, n, max_points, cap, index ? 0 : (long long)n_frames * cells, true);
+    if (workspace_bytes < w.bytes) return CPD_ERR_WORKSPACE;
     int32_t *const vid_ws = w.vid;          // the workspace's own [n] words (below, w.vid may become the index's rank -> row map)
     if (index) {
         const int32_t shape[3] = {geo.g[0] + z_extra, geo.g[1], geo.g[2]};
@@ -734,9 +744,7 @@ static int voxelize_batch_impl(const float *points, const float *const *frame_po
         CPD_HIP_TRY(hipMemsetAsync(v.flags, 0, 4, s));
         if (!canonical) CPD_HIP_TRY(hipMemsetAsync(v.flags, 1, 1, s));          // flags[0] = 1: row id = perm[rank]; canonical: rank
     }
-    int32_t *frame_base = (int32_t *)((char *)workspace + w.bytes);
-    int32_t *out_base = frame_base + CPD_VOX_MAX_FRAMES + 1;
-    int32_t *total = out_base + CPD_VOX_MAX_FRAMES + 1;
+    int32_t *const frame_base = w.frame_base, *const out_base = w.out_base, *const total = w.total;
     if (n == 0) {
         CPD_HIP_TRY(hipMemsetAsync(n_voxels, 0, (size_t)(n_frames + 1) * 4, s));
         if (index) {                                          // an empty but valid index

@@ -163,7 +163,7 @@ def order_rows_by_taps(indices, index, ksize=(3, 3, 3), chunk_rows=4096):
     new_to_old = torch.empty((n,), dtype=torch.int32, device=dev)
     old_to_new = torch.empty((n,), dtype=torch.int32, device=dev)
     out = torch.empty_like(indices)
-    ws = torch.empty((max(n, 1) * 4,), dtype=torch.uint8, device=dev)
+    ws = torch.empty((lib().cpd_order_rows_by_taps_workspace_bytes(n),), dtype=torch.uint8, device=dev)
     check(lib().cpd_order_rows_by_taps(ptr(indices), n, index.batch, iarr(index.shape), iarr(ksize), ptr(index.buf), int(chunk_rows),
                                        ptr(new_to_old), ptr(old_to_new), ptr(out), ptr(ws), ws.numel(), stream()), "cpd_order_rows_by_taps")
     return out, new_to_old, old_to_new
@@ -179,8 +179,7 @@ def order_rows_bricks(indices, index, brick=(8, 8), tile_rows=128):
     new_to_old = torch.empty((n,), dtype=torch.int32, device=dev)
     old_to_new = torch.empty((n,), dtype=torch.int32, device=dev)
     out = torch.empty_like(indices)
-    a = lambda b: (b + 255) // 256 * 256
-    ws = torch.empty((2 * a(4 * max(n, 1)) + a(16 * max(n, 1)),), dtype=torch.uint8, device=dev)
+    ws = torch.empty((lib().cpd_order_rows_bricks_workspace_bytes(n),), dtype=torch.uint8, device=dev)
     check(lib().cpd_order_rows_bricks(ptr(indices), n, index.batch, iarr(index.shape), ptr(index.buf), int(brick[0]), int(brick[1]), int(tile_rows),
                                       ptr(new_to_old), ptr(old_to_new), ptr(out), ptr(ws), ws.numel(), stream()), "cpd_order_rows_bricks")
     return out, new_to_old, old_to_new

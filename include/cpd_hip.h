@@ -132,11 +132,12 @@ int cpd_index_build(const int32_t *indices, int n, int batch, const int32_t shap
  * index, a permutation that sorts the rows of every chunk of `chunk_rows` consecutive rows (1024, 4096, 8192 or 16384) by their
  * neighbour pattern under the sub-manifold kernel `ksize` (<= 32 taps): new_to_old [n], old_to_new [n], and (optional)
  * indices_out [n][4] = the site list in the new order. Rows ordered this way make cpd_gather_conv's 16-row tap skipping nearly
- * exact (executed / useful MFMAs 1.3-1.55 -> 1.06-1.12 on Waymo-shape levels) at unchanged cache locality. workspace: n * 4
- * bytes. cpd_index_set_order installs a caller-owned rank -> row map (old_to_new; NULL = canonical again) in a site index:
+ * exact (executed / useful MFMAs 1.3-1.55 -> 1.06-1.12 on Waymo-shape levels) at unchanged cache locality. workspace:
+ * cpd_order_rows_by_taps_workspace_bytes(n) = max(n, 1) * 4 bytes (one word per row, not rounded up). cpd_index_set_order installs a caller-owned rank -> row map (old_to_new; NULL = canonical again) in a site index:
  * every lookup through that index (cpd_rulebook_subm / _conv, cpd_voxel_query_index) then returns rows in the new order, so a
  * level is re-ordered by passing its site list in the new order and installing the map -- no kernel sees a difference. The map
  * must outlive the index's use. */
+size_t cpd_order_rows_by_taps_workspace_bytes(int n);
 int cpd_order_rows_by_taps(const int32_t *indices, int n, int batch, const int32_t shape_zyx[3],
                            const int32_t ksize[3], const void *index, int chunk_rows, int32_t *new_to_old,
                            int32_t *old_to_new, int32_t *indices_out, void *workspace, size_t workspace_bytes,
@@ -148,7 +149,8 @@ int cpd_index_set_order(void *index, const int32_t *rank_to_row, cpd_stream_t st
  * sub-manifold neighbour pattern (what cpd_order_rows_by_taps does per chunk). A tile of 128 output rows then touches ~2.9 distinct
  * input rows per row instead of 4.5 (canonical) or 8.8 (4096-row pattern chunks): what cpd_gather_conv_planned stages in LDS.
  * `indices` [n][4]: the CANONICAL list of the level, `index`: its canonical index. Outputs as cpd_order_rows_by_taps.
- * workspace: 2 * align256(4 n) + align256(16 n) bytes. */
+ * workspace: cpd_order_rows_bricks_workspace_bytes(n) bytes. */
+size_t cpd_order_rows_bricks_workspace_bytes(int n);
 int cpd_order_rows_bricks(const int32_t *indices, int n, int batch, const int32_t shape_zyx[3], const void *index,
                           int brick_y, int brick_x, int tile_rows, int32_t *new_to_old, int32_t *old_to_new, int32_t *indices_out,
                           void *workspace, size_t workspace_bytes, cpd_stream_t stream);

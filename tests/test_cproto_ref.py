@@ -190,24 +190,11 @@ def test_sequence_generator():
     assert not np.array_equal(infos[0]["pose"], infos[1]["pose"])
 
 
-def _header_params(name):
-    txt = open(os.path.join(REPO, "include", "cpd_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % name, txt, flags=re.S)
-    assert m, "%s is not declared in include/cpd_hip.h" % name
-    return [p.strip() for p in m.group(1).split(",")]
-
-
 def test_abi_entry_points_and_error_codes():
     from cpd_amd import _lib
     lib = _lib.lib()
-    for name in ENTRY_POINTS:
+    for name in ENTRY_POINTS:                                            # (argument types: test_abi checks every row of the table)
         assert hasattr(lib, name), name
-        params = _header_params(name)
-        assert len(_lib.SIGNATURES[name][1]) == len(params), name
-        for ctype, decl in zip(_lib.SIGNATURES[name][1], params):      # pointers to pointers, scalars to scalars
-            is_ptr = "*" in decl or decl.startswith("cpd_stream_t")
-            assert is_ptr == (ctype in (ctypes.c_void_p, _lib._I3)), "%s: %s" % (name, decl)
         want = ctypes.c_size_t if name.endswith("_workspace_bytes") else ctypes.c_int
         assert _lib.SIGNATURES[name][0] is want
     txt = open(os.path.join(REPO, "include", "cpd_hip.h")).read()

@@ -592,6 +592,33 @@ def test_g_refusals(hip):
         assert rc == want and untouched(n2o) and untouched(o2n) and untouched(out)
 
 
+@gpu
+@pytest.mark.parametrize("n", [1, 65])
+def test_g_row_orders_refuse_a_short_workspace(hip, n):
+    """Both row orders check their workspace against their own size query: a view 256 bytes shorter than the query's answer (for
+    cpd_order_rows_by_taps, whose answer is 4 n bytes and not rounded up, as many bytes shorter as there are) is refused with
+    CPD_ERR_WORKSPACE and nothing is written. The view is the head of a buffer of the full size, so a check that wrongly let the
+    call through would still write inside the allocation."""
+    shape = [2, 8, 8]
+    ix, lst, _ = make_index(R.gen_full(1, shape)[:n], 1, shape, "canonical")
+    assert len(lst) == n
+    d_in = dev(lst.reshape(-1, 4))
+    for name in ("bricks", "by_taps"):
+        need = getattr(L(), "cpd_order_rows_%s_workspace_bytes" % name)(n)
+        full = poison(need)
+        view = full[:max(need - 256, 0)]                             # same base address as `full`
+        assert view.numel() < need
+        n2o, o2n, out = fenced(n), fenced(n), fenced(4 * n)
+        tail = (_lib.ptr(n2o), _lib.ptr(o2n), _lib.ptr(out), _lib.ptr(full), view.numel(), _lib.stream())
+        if name == "bricks":
+            rc = L().cpd_order_rows_bricks(_lib.ptr(d_in), n, ix.batch, _lib.iarr(ix.shape), ix.ptr(), 8, 8, 128, *tail)
+        else:
+            rc = L().cpd_order_rows_by_taps(_lib.ptr(d_in), n, ix.batch, _lib.iarr(ix.shape), _lib.iarr([3, 3, 3]), ix.ptr(), 4096, *tail)
+        assert rc == WORKSPACE, name
+        assert untouched(n2o) and untouched(o2n) and untouched(out) and bool((full == POISON).all().item()), name
+    assert ix.guard_ok()
+
+
 V_SHAPE = [5, 600, 500]              # the index's grid: the voxel grid 4 x 600 x 500 and one more z-level (the backbone's sparse shape)
 V_VSIZE, V_RANGE = [1.0, 1.0, 1.0], [0.0, 0.0, 0.0, 500.0, 600.0, 4.0]
 V_BLOCK = 64 * SCAN_TILE             # cells per scan block: 524.288 x-lines of 500 cells -- block edges fall inside lines, bands and bricks
