@@ -218,8 +218,11 @@ __device__ __forceinline__ void cells_within(float q, float radius, float s, flo
     const float a = (q - radius - o) * inv - 0.5f - 1e-3f, b = (q + radius - o) * inv - 0.5f + 1e-3f;
     lo = c0 - range < 0 ? 0 : c0 - range;
     hi = c0 + range >= n ? n - 1 : c0 + range;
-    if (a > (float)lo) lo = (int)ceilf(a);          // (a, b beyond the int range only for coordinates no grid has; the comparisons guard them)
-    if (b < (float)hi) hi = (int)floorf(b);
+    // a, b are converted only where they lie inside the window: beyond it (a coordinate no grid has, up to infinity) the interval is empty,
+    // [hi + 1, hi] or [lo, lo - 1], and nothing overflows in the callers' hi - lo + 1; NaN bounds fail every comparison and keep the window
+    const int wlo = lo, whi = hi;
+    if (a > (float)wlo) lo = a > (float)whi ? whi + 1 : (int)ceilf(a);
+    if (b < (float)whi) hi = b < (float)wlo ? wlo - 1 : (int)floorf(b);
 }
 __global__ void __launch_bounds__(256) voxel_query_grid_kernel(QueryParams p, IndexLookup lookup, CellGeom cg, float radius) {
     const int lane = threadIdx.x & 63, sub = lane & 15, grp = lane >> 4;
@@ -234,10 +237,14 @@ __global__ void __launch_bounds__(256) voxel_query_grid_kernel(QueryParams p, In
     }
     // the part of the window the ball can reach: rows [zlo, zhi] x [ylo, yhi] in (z, y) order -- the reference's scan order restricted to
     // them --, cells [xlo, xhi] of each (<= 2 xr + 1 <= 32 bits of the bitmap)
+    // A NaN coordinate makes the reference's d2 NaN, and `not >` takes every occupied cell of the window whatever its other two
+    // offsets are: nothing may be pruned then. `wild` is 0 for a finite point and NaN otherwise; added to the radius it turns both
+    // bounds of cells_within into NaN (whole window kept), added to a row's b2 + c2 it keeps the row.
+    const float wild = (nx + ny + nz) * 0.f;
     int zlo, zhi, ylo, yhi, xlo, xhi;
-    cells_within(nz, radius, cg.sz, cg.oz, cz, p.zr, p.r1, zlo, zhi);
-    cells_within(ny, radius, cg.sy, cg.oy, cy, p.yr, p.r2, ylo, yhi);
-    cells_within(nx, radius, cg.sx, cg.ox, cx, p.xr, p.r3, xlo, xhi);
+    cells_within(nz, radius + wild, cg.sz, cg.oz, cz, p.zr, p.r1, zlo, zhi);
+    cells_within(ny, radius + wild, cg.sy, cg.oy, cy, p.yr, p.r2, ylo, yhi);
+    cells_within(nx, radius + wild, cg.sx, cg.ox, cx, p.xr, p.r3, xlo, xhi);
     const int wy = yhi - ylo + 1, nbits = xhi - xlo + 1;
     const int nrow = (live && wy > 0 && nbits > 0 && zhi >= zlo) ? (zhi - zlo + 1) * wy : 0;
     const float inv_wy = 1.0f / (float)(wy > 0 ? wy : 1);
@@ -253,7 +260,7 @@ __global__ void __launch_bounds__(256) voxel_query_grid_kernel(QueryParams p, In
             const int z = zlo + qz, y = ylo + (rr - qz * wy);
             const float yp = ((float)y + 0.5f) * cg.sy + cg.oy, zp = ((float)z + 0.5f) * cg.sz + cg.oz;
             const float b2 = (yp - ny) * (yp - ny), c2 = (zp - nz) * (zp - nz);
-            if (!(b2 + c2 > p.radius2)) {
+            if (!(b2 + c2 + wild > p.radius2)) {
                 key0 = (((long long)b * p.r1 + z) * p.r2 + y) * p.r3 + xlo;
                 const long long w0 = key0 >> 6;
                 const int off = (int)(key0 & 63);
@@ -362,7 +369,7 @@ __global__ void __launch_bounds__(256) voxel_pool_max_kernel(int m, int c, int n
             const float dx = xyz[3 * (size_t)j] - nx, dy = xyz[3 * (size_t)j + 1] - ny, dz = xyz[3 * (size_t)j + 2] - nz;
             const float pos = ((dx * w0 + dy * w1) + dz * w2) + b0;
             const float v = fin[(size_t)j * fin_ld + ch] + pos;
-            best = v > best ? v : best;
+            best = (v > best || v != v) ? v : best;          // a NaN is taken and then kept (nothing compares above it), like torch's max
         }
     }
     out[(size_t)pt * out_ld + ch] = best;
@@ -415,7 +422,7 @@ __global__ void __launch_bounds__(256) voxel_pool_max_mlp_kernel(int m, int nsam
                     const float dx = xyz[3 * (size_t)j] - nx, dy = xyz[3 * (size_t)j + 1] - ny, dz = xyz[3 * (size_t)j + 2] - nz;
                     const float pos = ((dx * w0 + dy * w1) + dz * w2) + b0;
                     const float v = fin[(size_t)j * fin_ld + ch] + pos;
-                    best = v > best ? v : best;
+                    best = (v > best || v != v) ? v : best;         // (a NaN is taken and kept, as in voxel_pool_max_kernel)
                 }
             }
         }
@@ -435,7 +442,7 @@ __global__ void __launch_bounds__(256) voxel_pool_max_mlp_kernel(int m, int nsam
                 acc += v.w * wcol[q][k + 3];
             }
             acc += tcol[q];
-            if (relu) acc = acc > 0.f ? acc : 0.f;
+            if (relu) acc = (acc > 0.f || acc != acc) ? acc : 0.f;       // torch's ReLU keeps a NaN
             if (live && co < c2) {
                 out[(size_t)pt * out_ld + co] = acc;
                 const uint32_t vb = __float_as_uint(acc) & 0x7fffffffu;      // (absmax_note() spelled out: with the helper every instantiation's SGPR count moves by two)

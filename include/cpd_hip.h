@@ -887,7 +887,8 @@ int cpd_group_points_grad(int b, int m, int c, int nsample, int n, const float *
  * (voxel_pool_modules.py:96-117): out[m][ch] = max_s relu(features_in[idx[m][s]][ch] +
  * (xyz[idx[m][s]] - new_xyz[m]) . w_pos[:, ch] + b_pos[ch]), relu(b_pos[ch]) for an empty ball
  * (idx[m][0] < 0). idx holds global rows; w_pos [3, c] / b_pos [c] = Conv2d(3, c) with its
- * eval BatchNorm folded. */
+ * eval BatchNorm folded. A NaN feature or offset in a ball gives NaN (torch's ReLU and max), here and through the
+ * output MLP of cpd_voxel_pool_max_mlp below: the range block of the _ranged form then holds a NaN's bits. */
 int cpd_voxel_pool_max(int m, int c, int nsample, const float *features_in, int features_ld,
                        const float *xyz, const float *new_xyz, const int32_t *idx, const float *w_pos,
                        const float *b_pos, float *out, int out_ld, cpd_stream_t stream);
