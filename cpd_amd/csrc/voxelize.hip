@@ -9,14 +9,17 @@
 //   1 keys      : cell key per point (fp32 floor((p-lo)/vs), IEEE division), occupancy bit set
 //                 in a dense bitmap over the grid (1 bit per cell; 92.7 M cells = 11.6 MB for the
 //                 Waymo grid -- trivially resident in 288 GB HBM / 256 MB Infinity Cache)
-//   2 scan      : popcount prefix over the bitmap  -> dense rank r of every occupied cell
+//   2 scan      : popcount prefix over the bitmap  -> dense rank r of every occupied cell (only the
+//                 32 KB blocks of the bitmap that hold a bit are visited)
 //   3 first     : first[r] = min point index (atomicMin)
 //   4 order     : flag(i) = (first[rank_i] == i); prefix sum over POINT order of the flags gives
 //                 the serial first-appearance voxel id; ids >= max_voxels are dropped exactly as
-//                 the serial scan would
+//                 the serial scan would (frames + assign: per-frame counts, output rows, coords)
 //   5 insert    : per voxel, the P smallest point indices via an atomicMin insertion cascade
 //   6 gather    : coalesced copy of the kept points into voxels[M,P,C], count, mean
 // HBM traffic is ~ the points read 3x (12 B/pt keys + rows) + outputs; see DESIGN.md.
+// There is ONE first-appearance implementation, written for a batch of frames (below): cpd_voxelize is
+// its one-frame call. The engine-internal canonical row order has its own point-list build (round 3).
 #include "common.h"
 #include <string.h>
 #include "site_index_layout.h"
@@ -80,21 +83,21 @@ struct VoxWs {
     uint32_t *base;     // [words] popcount prefix
     uint32_t *bsum_bm;  // scan block sums (bitmap)
     uint32_t *bsum_pt;  // scan block sums (points)
-    int32_t *pkey;      // [n] cell key or -1
+    int32_t *pkey;      // [n] cell key inside the point's frame, or -1
     int32_t *prank;     // [n] dense rank of the point's cell
     int32_t *first;     // [n] min point index per rank
-    int32_t *vid;       // [n] voxel id per rank
+    int32_t *vid;       // [n] per rank: global voxel id, then output row (-1: beyond its frame's max_voxels)
     int32_t *slots;     // [cap*P] kept point indices per voxel (sorted ascending)
     int32_t *counts;    // [cap] points seen per voxel
     int32_t *nocc;      // scalar: occupied cells
-    int32_t *frame_base = nullptr;  // batched entry points only: [CPD_VOX_MAX_FRAMES + 1] first global voxel id per frame,
-    int32_t *out_base = nullptr;    //   [CPD_VOX_MAX_FRAMES + 1] first output row per frame,
-    int32_t *total = nullptr;       //   scalar: voxels over all frames
+    int32_t *frame_base;  // [CPD_VOX_MAX_FRAMES + 1] first global voxel id per frame
+    int32_t *out_base;    // [CPD_VOX_MAX_FRAMES + 1] first output row per frame; [n_frames]: rows of all frames (max_voxels applied)
+    int32_t *total;       // scalar: voxels over all frames (max_voxels not applied)
     long long words;
     size_t bytes;
 };
 
-static VoxWs carve(void *ws, int n, int P, int cap, long long cells, bool batch) {
+static VoxWs carve(void *ws, int n, int P, int cap, long long cells) {
     VoxWs w;
     Carve c;
     w.words = (cells + 63) / 64;
@@ -110,55 +113,12 @@ static VoxWs carve(void *ws, int n, int P, int cap, long long cells, bool batch)
     w.slots = ws_at<int32_t>(ws, c.take((size_t)(cap > 0 ? cap : 1) * P * 4));
     w.counts = ws_at<int32_t>(ws, c.take((size_t)(cap > 0 ? cap : 1) * 4));
     w.nocc = ws_at<int32_t>(ws, c.take(4));
-    if (batch) {
-        const size_t per_frame = (CPD_VOX_MAX_FRAMES + 1) * 4, tail = c.take(2 * per_frame + 16);
-        w.frame_base = ws_at<int32_t>(ws, tail);
-        w.out_base = ws_at<int32_t>(ws, tail + per_frame);
-        w.total = ws_at<int32_t>(ws, tail + 2 * per_frame);
-    }
+    const size_t per_frame = (CPD_VOX_MAX_FRAMES + 1) * 4, tail = c.take(2 * per_frame + 16);
+    w.frame_base = ws_at<int32_t>(ws, tail);
+    w.out_base = ws_at<int32_t>(ws, tail + per_frame);
+    w.total = ws_at<int32_t>(ws, tail + 2 * per_frame);
     w.bytes = c.o;
     return w;
-}
-
-__global__ void __launch_bounds__(256) vox_keys_kernel(const float *__restrict__ pts, int n, int c, VoxGeom geo,
-                                                       int32_t *__restrict__ pkey, uint64_t *bitmap) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float *p = pts + (size_t)i * c;
-    int32_t cz[3];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {  // j over z,y,x ; coordinate axis 2-j
-        // fp32 subtract then IEEE-correct fp32 divide then floor: bit-identical to the serial CPU
-        // voxelizer at voxel boundaries (no reciprocal multiply, no contraction possible here).
-        float f = floorf(__fdiv_rn(__fsub_rn(p[2 - j], geo.lo[2 - j]), geo.vs[2 - j]));
-        if (!(f >= 0.0f) || !(f < (float)geo.g[j])) ok = false;
-        cz[j] = ok ? (int32_t)f : 0;
-    }
-    int32_t key = -1;
-    if (ok) {
-        key = (cz[0] * geo.g[1] + cz[1]) * geo.g[2] + cz[2];
-        atomicOr((unsigned long long *)&bitmap[key >> 6], 1ull << (key & 63));
-    }
-    pkey[i] = key;
-}
-
-__global__ void __launch_bounds__(256) vox_first_kernel(int n, const int32_t *__restrict__ pkey,
-                                                        const uint64_t *__restrict__ bitmap,
-                                                        const uint32_t *__restrict__ base, int32_t *__restrict__ prank,
-                                                        int32_t *first) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int32_t key = pkey[i];
-    int32_t r = -1;
-    const int32_t prev = __shfl_up(key, 1);     // (all lanes of a wave reach this: the early return above is per block tail only)
-    if (key >= 0) {
-        uint64_t w = bitmap[key >> 6];
-        r = (int32_t)(base[key >> 6] + __popcll(w & ((1ull << (key & 63)) - 1ull)));
-        // a lane whose left neighbour has the same key cannot hold the voxel's first point
-        if ((threadIdx.x & 63) == 0 || prev != key) atomicMin(&first[r], i);
-    }
-    prank[i] = r;
 }
 
 struct FlagFn {  // 1 iff point i is the first point of its voxel
@@ -169,27 +129,6 @@ struct FlagFn {  // 1 iff point i is the first point of its voxel
         return (r >= 0 && first[r] == (int32_t)i) ? 1u : 0u;
     }
 };
-struct AssignVoxelFn {  // flagged point i starts voxel id = prefix (serial first-appearance order)
-    const int32_t *prank;
-    const int32_t *pkey;
-    int32_t *vid;
-    int32_t *coords;
-    int coord_cols, batch_idx, max_voxels;
-    int32_t gy, gx;
-    __device__ void operator()(long long i, uint32_t flag, uint32_t prefix) const {
-        if (!flag) return;
-        int32_t v = (int32_t)prefix;
-        vid[prank[i]] = v;
-        if (v < max_voxels) {
-            int32_t key = pkey[i];
-            int32_t x = key % gx, y = (key / gx) % gy, z = key / (gx * gy);
-            int32_t *o = coords + (size_t)v * coord_cols;
-            if (coord_cols == 4) { o[0] = batch_idx; o[1] = z; o[2] = y; o[3] = x; }
-            else { o[0] = z; o[1] = y; o[2] = x; }
-        }
-    }
-};
-
 struct PopcFn {
     const uint64_t *bitmap;
     __device__ uint32_t operator()(long long w) const { return (uint32_t)__popcll(bitmap[w]); }
@@ -199,53 +138,8 @@ struct StoreBaseFn {
     __device__ void operator()(long long w, uint32_t, uint32_t prefix) const { base[w] = prefix; }
 };
 
-__global__ void __launch_bounds__(256) vox_insert_kernel(int n, int P, int max_voxels,
-                                                         const int32_t *__restrict__ prank,
-                                                         const int32_t *__restrict__ vid, const int32_t *__restrict__ first,
-                                                         int32_t *slots, int32_t *counts) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int32_t r = prank[i];
-    if (r < 0) return;
-    int32_t v = vid[r];
-    if (v >= max_voxels) return;
-    atomicAdd(&counts[v], 1);
-    // Insertion cascade: slot p ends up holding the (p+1)-th smallest point index of the voxel. Slot 0 is the voxel's first
-    // point (known from vox_first: a plain store); every other value enters at slot 1, whatever loses an atomicMin moves on.
-    int32_t x = i;
-    int32_t *s = slots + (size_t)v * P;
-    if (first[r] == i) { s[0] = i; return; }
-    for (int p = 1; p < P; ++p) {
-        int32_t old = atomicMin(&s[p], x);
-        if (old == 0x7f7f7f7f) break;  // slot was empty: nothing displaced
-        x = old > x ? old : x;
-    }
-}
-
-__global__ void __launch_bounds__(256) vox_gather_kernel(const float *__restrict__ pts, int c, int P, int cap,
-                                                         const int32_t *__restrict__ n_vox,
-                                                         const int32_t *__restrict__ slots,
-                                                         const int32_t *__restrict__ counts, float *voxels,
-                                                         int32_t *num_points, float *mean) {
-    long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    int v = (int)(tid / c), ch = (int)(tid % c);
-    if (v >= cap || v >= *n_vox) return;
-    int cnt = counts[v];
-    if (cnt > P) cnt = P;
-    float s = 0.f;
-    for (int p = 0; p < P; ++p) {  // sum order p = 0..P-1, zeros included (mean_vfe.py:41)
-        float val = 0.f;
-        if (p < cnt) val = pts[(size_t)slots[(size_t)v * P + p] * c + ch];
-        if (voxels) voxels[((size_t)v * P + p) * c + ch] = val;
-        s += val;
-    }
-    if (mean) mean[(size_t)v * c + ch] = __fdiv_rn(s, (float)(cnt < 1 ? 1 : cnt));
-    if (ch == 0) num_points[v] = cnt;
-}
-
-
 // ------------------------------------------------------------------------------------------
-// Batched voxelizer: all frames of a batch in ONE set of launches. Points are concatenated in frame
+// The voxelizer proper: all frames of a batch (one frame for cpd_voxelize) in ONE set of launches. Points are concatenated in frame
 // order, a cell key carries the frame (key = frame * cells + cell) and the occupancy bitmap spans
 // batch x grid; the first-appearance scan then runs over the concatenation, which keeps every
 // frame's serial order, and a per-frame base turns global ids into the per-frame voxel ids the
@@ -368,8 +262,10 @@ struct AssignGlobalFn {  // flagged point i starts the voxel with GLOBAL id = pr
     }
 };
 
+// n_voxels [nf] = voxels per frame; n_total (may be null: cpd_voxelize's n_voxels is ONE int) = their sum, which out_base[nf] holds
+// in any case
 __global__ void vox_frames_kernel(FrameOffsets fo, int n, int max_voxels, int32_t *frame_base, const int32_t *total,
-                                  int32_t *out_base, int32_t *n_voxels) {
+                                  int32_t *out_base, int32_t *n_voxels, int32_t *n_total) {
     if (threadIdx.x != 0) return;
     int32_t acc = 0;
     for (int f = 0; f < fo.nf; ++f) {
@@ -382,7 +278,7 @@ __global__ void vox_frames_kernel(FrameOffsets fo, int n, int max_voxels, int32_
         acc += cnt;
     }
     out_base[fo.nf] = acc;
-    n_voxels[fo.nf] = acc;
+    if (n_total) *n_total = acc;
 }
 
 __global__ void __launch_bounds__(256) vox_assign_batch_kernel(int n, FrameOffsets fo, int max_voxels,
@@ -391,7 +287,8 @@ __global__ void __launch_bounds__(256) vox_assign_batch_kernel(int n, FrameOffse
                                                                const int32_t *__restrict__ first,
                                                                const int32_t *__restrict__ frame_base,
                                                                const int32_t *__restrict__ out_base, int32_t *vid,
-                                                               int32_t *coords, int32_t gy, int32_t gx) {
+                                                               int32_t *coords, int coord_cols, int coord_base, int32_t gy,
+                                                               int32_t gx) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int32_t r = prank[i];
@@ -402,8 +299,9 @@ __global__ void __launch_bounds__(256) vox_assign_batch_kernel(int n, FrameOffse
     const int32_t row = out_base[f] + local;
     vid[r] = row;
     const int32_t key = pkey[i];                                // the cell inside the frame
-    int32_t *o = coords + (size_t)row * 4;
-    o[0] = f; o[1] = key / (gx * gy); o[2] = (key / gx) % gy; o[3] = key % gx;
+    int32_t *o = coords + (size_t)row * coord_cols;              // (z, y, x), or (coord_base + frame, z, y, x)
+    if (coord_cols == 4) *o++ = coord_base + f;
+    o[0] = key / (gx * gy); o[1] = (key / gx) % gy; o[2] = key % gx;
 }
 
 // Canonical row order (engine-internal; the boundary's order is first appearance): row = rank of the voxel's cell in the occupancy
@@ -426,18 +324,6 @@ __global__ void vox_frames_canonical_kernel(int nf, long long cells, const uint6
     if (f < nf) n_voxels[f] = rank_at(f + 1) - rank_at(f);
     if (f == 0) n_voxels[nf] = *total;
 }
-__global__ void __launch_bounds__(256) vox_assign_canonical_kernel(int n, FrameOffsets fo, const int32_t *__restrict__ pkey,
-                                                                   const int32_t *__restrict__ prank, const int32_t *__restrict__ first,
-                                                                   int32_t *coords, int32_t gy, int32_t gx) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t r = prank[i];
-    if (r < 0 || first[r] != i) return;
-    const int32_t key = pkey[i];
-    int32_t *o = coords + (size_t)r * 4;
-    o[0] = fo.frame_of(i); o[1] = key / (gx * gy); o[2] = (key / gx) % gy; o[3] = key % gx;
-}
-
 // Consecutive returns of a beam often fall into one voxel: lanes of a wave with the same voxel form a RUN (in point order).
 // The run's last lane adds the run length to the voxel's count in one atomic, and a lane that has max_points earlier lanes of
 // its own run can never hold one of the voxel's max_points smallest indices, so it skips the cascade altogether.
@@ -451,7 +337,7 @@ __global__ void __launch_bounds__(256) vox_insert_batch_kernel(int n, int P, con
     if (i < n) {
         const int32_t r = prank[i];
         if (r >= 0) {
-            v = vid ? vid[r] : r;                                // < 0: voxel beyond its frame's max_voxels; no map: row = rank
+            v = vid[r];                                          // < 0: voxel beyond its frame's max_voxels
             is_first = first[r] == i;
         }
     }
@@ -623,57 +509,7 @@ static int vox_geom(const float vs[3], const float rg[6], VoxGeom *g, long long 
     return CPD_OK;
 }
 
-extern "C" size_t cpd_voxelize_workspace_bytes(int n_points, int max_points, int max_voxels, const float vsize_xyz[3],
-                                               const float range_xyz[6]) {
-    VoxGeom g;
-    long long cells;
-    if (n_points < 0 || max_points <= 0 || max_voxels <= 0) return 0;
-    if (vox_geom(vsize_xyz, range_xyz, &g, &cells)) return 0;
-    int cap = max_voxels < n_points ? max_voxels : n_points;
-    return carve(nullptr, n_points, max_points, cap, cells, false).bytes;
-}
-
-extern "C" int cpd_voxelize(const float *points, int n_points, int c, const float vsize_xyz[3],
-                            const float range_xyz[6], int max_points, int max_voxels, int batch_idx, int coord_cols,
-                            float *voxels, int32_t *coords, int32_t *num_points, float *mean_features,
-                            int32_t *n_voxels, void *workspace, size_t workspace_bytes, cpd_stream_t stream) {
-    if (n_points < 0 || c < 3 || max_points <= 0 || max_voxels <= 0 || !coords || !num_points || !n_voxels ||
-        !workspace || (coord_cols != 3 && coord_cols != 4) || (n_points > 0 && !points))
-        return CPD_ERR_ARG;
-    VoxGeom geo;
-    long long cells;
-    int rc = vox_geom(vsize_xyz, range_xyz, &geo, &cells);
-    if (rc) return rc;
-    hipStream_t s = cpd_s(stream);
-    const int n = n_points;
-    const int cap = max_voxels < n ? max_voxels : n;
-    VoxWs w = carve(workspace, n, max_points, cap, cells, false);
-    if (workspace_bytes < w.bytes) return CPD_ERR_WORKSPACE;
-    if (n == 0) {
-        CPD_HIP_TRY(hipMemsetAsync(n_voxels, 0, 4, s));
-        return CPD_OK;
-    }
-    CPD_HIP_TRY(hipMemsetAsync(w.bitmap, 0, (size_t)w.words * 8, s));
-    CPD_HIP_TRY(hipMemsetAsync(w.first, 0x7f, (size_t)n * 4, s));
-    CPD_HIP_TRY(hipMemsetAsync(w.slots, 0x7f, (size_t)cap * max_points * 4, s));
-    CPD_HIP_TRY(hipMemsetAsync(w.counts, 0, (size_t)cap * 4, s));
-    const int nb = cpd_div_up(n, 256);
-    vox_keys_kernel<<<nb, 256, 0, s>>>(points, n, c, geo, w.pkey, w.bitmap);
-    rc = device_scan(w.words, PopcFn{w.bitmap}, StoreBaseFn{w.base}, w.bsum_bm, w.nocc, -1, s);
-    if (rc) return rc;
-    vox_first_kernel<<<nb, 256, 0, s>>>(n, w.pkey, w.bitmap, w.base, w.prank, w.first);
-    rc = device_scan(n, FlagFn{w.prank, w.first},
-                     AssignVoxelFn{w.prank, w.pkey, w.vid, coords, coord_cols, batch_idx, max_voxels, geo.g[1], geo.g[2]},
-                     w.bsum_pt, n_voxels, max_voxels, s);
-    if (rc) return rc;
-    vox_insert_kernel<<<nb, 256, 0, s>>>(n, max_points, max_voxels, w.prank, w.vid, w.first, w.slots, w.counts);
-    const long long threads = (long long)cap * c;
-    vox_gather_kernel<<<cpd_div_up(threads, 256), 256, 0, s>>>(points, c, max_points, cap, n_voxels, w.slots, w.counts,
-                                                               voxels, num_points, mean_features);
-    return cpd_check_launch();
-}
-
-// ---- batched entry points ---------------------------------------------------------------------
+// ---- entry points -----------------------------------------------------------------------------
 static int batch_caps(int n_total, int n_frames, int max_voxels, long long cells, int *cap) {
     if (n_frames <= 0 || n_frames > CPD_VOX_MAX_FRAMES) return CPD_ERR_UNSUPPORTED;
     if (cells >= (1ll << 31) || (long long)n_frames * cells >= (1ll << 40)) return CPD_ERR_UNSUPPORTED;
@@ -690,17 +526,19 @@ extern "C" size_t cpd_voxelize_batch_workspace_bytes(int n_total, int n_frames, 
     if (n_total < 0 || max_points <= 0 || max_voxels <= 0) return 0;
     if (vox_geom(vsize_xyz, range_xyz, &g, &cells)) return 0;
     if (batch_caps(n_total, n_frames, max_voxels, cells, &cap)) return 0;
-    return carve(nullptr, n_total, max_points, cap, (long long)n_frames * cells, true).bytes;
+    return carve(nullptr, n_total, max_points, cap, (long long)n_frames * cells).bytes;
 }
 
 // `index` != NULL: the occupancy bitmap, its popcount prefix and the rank -> row map are built INSIDE that site index (of
 // the grid with z_extra more z-levels -- the backbone's sparse_shape = grid + [1,0,0], spconv_backbone.py:412), which is
 // then the level-0 index of the sparse tensor as it stands: no second bitmap, mark, scan and permutation pass.
+// First-appearance rows (canonical = 0) carry coord_cols = 3: (z, y, x) or 4: (coord_base + frame, z, y, x) coordinates; n_voxels
+// holds n_frames counts and, with `with_total`, their sum behind them.
 static int voxelize_batch_impl(const float *points, const float *const *frame_points, const int32_t *frame_offsets, int n_frames, int c,
                                const float vsize_xyz[3], const float range_xyz[6], int max_points, int max_voxels,
                                float *voxels, int32_t *coords, int32_t *num_points, float *mean_features,
                                int32_t *n_voxels, void *workspace, size_t workspace_bytes, void *index, size_t index_bytes,
-                               int z_extra, int canonical, cpd_stream_t stream) {
+                               int z_extra, int canonical, int coord_cols, int coord_base, bool with_total, cpd_stream_t stream) {
     if (!frame_offsets || c < 3 || max_points <= 0 || max_voxels <= 0 || !coords || !num_points || !n_voxels || !workspace ||
         z_extra < 0)
         return CPD_ERR_ARG;
@@ -732,7 +570,7 @@ static int voxelize_batch_impl(const float *points, const float *const *frame_po
     hipStream_t s = cpd_s(stream);
     // with an index the bitmap / prefix / scan spine live there: the workspace (sized by cpd_voxelize_batch_workspace_bytes for
     // the plain grid) then carries no bitmap at all
-    VoxWs w = carve(workspace, n, max_points, cap, index ? 0 : (long long)n_frames * cells, true);
+    VoxWs w = carve(workspace, n, max_points, cap, index ? 0 : (long long)n_frames * cells);
     if (workspace_bytes < w.bytes) return CPD_ERR_WORKSPACE;
     int32_t *const vid_ws = w.vid;          // the workspace's own [n] words (below, w.vid may become the index's rank -> row map)
     if (index) {
@@ -744,9 +582,8 @@ static int voxelize_batch_impl(const float *points, const float *const *frame_po
         CPD_HIP_TRY(hipMemsetAsync(v.flags, 0, 4, s));
         if (!canonical) CPD_HIP_TRY(hipMemsetAsync(v.flags, 1, 1, s));          // flags[0] = 1: row id = perm[rank]; canonical: rank
     }
-    int32_t *const frame_base = w.frame_base, *const out_base = w.out_base, *const total = w.total;
     if (n == 0) {
-        CPD_HIP_TRY(hipMemsetAsync(n_voxels, 0, (size_t)(n_frames + 1) * 4, s));
+        CPD_HIP_TRY(hipMemsetAsync(n_voxels, 0, (size_t)(n_frames + (with_total ? 1 : 0)) * 4, s));
         if (index) {                                          // an empty but valid index
             CPD_HIP_TRY(hipMemsetAsync(w.bitmap, 0, (size_t)w.words * 8, s));
             CPD_HIP_TRY(hipMemsetAsync(w.base, 0, (size_t)w.words * 4, s));
@@ -759,9 +596,7 @@ static int voxelize_batch_impl(const float *points, const float *const *frame_po
     // kernel marks the blocks it sets bits in
     CPD_HIP_TRY(hipMemsetAsync(w.bsum_bm, 0, (size_t)scan_num_blocks(w.words) * 4, s));
     const int nb = cpd_div_up(n, 256);
-    bool cascade = false;                    // tuning only (CPD_TUNE=1 CPD_VOX_CASCADE=1): round 2's atomicMin cascade, for A/B timing
-    if (const char *e = cpd_knob(cpd_tuning(), "CPD_VOX_CASCADE")) cascade = atoi(e) != 0;
-    if (canonical && !cascade) {
+    if (canonical) {
         // rows = ranks: the max_voxels cap (defined on first-appearance order) is NOT applied -- the caller checks the per-frame
         // counts and falls back to the exact path if a frame exceeds it. Point lists by counting sort (above): ppos in w.first's
         // words, the compact list in w.slots' (cap * max_points >= n of them), the segment offsets in the workspace's vid words.
@@ -781,29 +616,42 @@ static int voxelize_batch_impl(const float *points, const float *const *frame_po
     }
     if (cpd_fill_bytes(w.first, 0x7f, (size_t)n * 4, s)) return CPD_ERR_LAUNCH;
     if (cpd_fill_bytes(w.slots, 0x7f, (size_t)cap * max_points * 4, s)) return CPD_ERR_LAUNCH;
-    CPD_HIP_TRY(hipMemsetAsync(frame_base, 0, (CPD_VOX_MAX_FRAMES + 1) * 4, s));
+    CPD_HIP_TRY(hipMemsetAsync(w.frame_base, 0, (CPD_VOX_MAX_FRAMES + 1) * 4, s));
     vox_keys_batch_kernel<<<nb, 256, 0, s>>>(fp, n, c, geo, cells, fo, w.pkey, w.bitmap, w.bsum_bm);
     rc = device_scan_touched(w.words, PopcFn{w.bitmap}, StoreBaseFn{w.base}, w.bsum_bm, w.nocc, -1, s);
     if (rc) return rc;
     vox_first_batch_kernel<<<nb, 256, 0, s>>>(n, cells, fo, w.pkey, w.bitmap, w.base, w.prank, w.first);
-    if (canonical) {
-        // rows = ranks: the max_voxels cap (defined on first-appearance order) is NOT applied -- the caller checks the per-frame
-        // counts and falls back to the exact path if a frame exceeds it
-        vox_frames_canonical_kernel<<<1, 64, 0, s>>>(n_frames, cells, w.bitmap, w.base, w.bsum_bm, w.nocc, n_voxels);
-        vox_assign_canonical_kernel<<<nb, 256, 0, s>>>(n, fo, w.pkey, w.prank, w.first, coords, geo.g[1], geo.g[2]);
-        vox_insert_batch_kernel<<<nb, 256, 0, s>>>(n, max_points, w.prank, nullptr, w.first, w.slots, w.counts);
-    } else {
-        rc = device_scan(n, FlagFn{w.prank, w.first}, AssignGlobalFn{w.prank, w.vid, frame_base, fo}, w.bsum_pt, total, -1, s);
-        if (rc) return rc;
-        vox_frames_kernel<<<1, 64, 0, s>>>(fo, n, max_voxels, frame_base, total, out_base, n_voxels);
-        vox_assign_batch_kernel<<<nb, 256, 0, s>>>(n, fo, max_voxels, w.pkey, w.prank, w.first, frame_base, out_base,
-                                                   w.vid, coords, geo.g[1], geo.g[2]);
-        vox_insert_batch_kernel<<<nb, 256, 0, s>>>(n, max_points, w.prank, w.vid, w.first, w.slots, w.counts);
-    }
+    rc = device_scan(n, FlagFn{w.prank, w.first}, AssignGlobalFn{w.prank, w.vid, w.frame_base, fo}, w.bsum_pt, w.total, -1, s);
+    if (rc) return rc;
+    vox_frames_kernel<<<1, 64, 0, s>>>(fo, n, max_voxels, w.frame_base, w.total, w.out_base, n_voxels,
+                                       with_total ? n_voxels + n_frames : nullptr);
+    vox_assign_batch_kernel<<<nb, 256, 0, s>>>(n, fo, max_voxels, w.pkey, w.prank, w.first, w.frame_base, w.out_base,
+                                               w.vid, coords, coord_cols, coord_base, geo.g[1], geo.g[2]);
+    vox_insert_batch_kernel<<<nb, 256, 0, s>>>(n, max_points, w.prank, w.vid, w.first, w.slots, w.counts);
     const long long threads = (long long)cap * c;
-    vox_gather_frames_kernel<<<cpd_div_up(threads, 256), 256, 0, s>>>(fp, fo, c, max_points, cap, n_voxels + n_frames, w.slots, w.counts,
+    // (the rows of all frames: out_base[n_frames], which is there whether or not n_voxels has a slot for the sum)
+    vox_gather_frames_kernel<<<cpd_div_up(threads, 256), 256, 0, s>>>(fp, fo, c, max_points, cap, w.out_base + n_frames, w.slots, w.counts,
                                                                       voxels, num_points, mean_features);
     return cpd_check_launch();
+}
+
+// One frame: the batch of one, with the caller's batch_idx in front of (z, y, x) when coord_cols = 4 and ONE int of n_voxels.
+extern "C" size_t cpd_voxelize_workspace_bytes(int n_points, int max_points, int max_voxels, const float vsize_xyz[3],
+                                               const float range_xyz[6]) {
+    return cpd_voxelize_batch_workspace_bytes(n_points, 1, max_points, max_voxels, vsize_xyz, range_xyz);
+}
+
+extern "C" int cpd_voxelize(const float *points, int n_points, int c, const float vsize_xyz[3],
+                            const float range_xyz[6], int max_points, int max_voxels, int batch_idx, int coord_cols,
+                            float *voxels, int32_t *coords, int32_t *num_points, float *mean_features,
+                            int32_t *n_voxels, void *workspace, size_t workspace_bytes, cpd_stream_t stream) {
+    if (n_points < 0 || c < 3 || max_points <= 0 || max_voxels <= 0 || !coords || !num_points || !n_voxels ||
+        !workspace || (coord_cols != 3 && coord_cols != 4) || (n_points > 0 && !points))
+        return CPD_ERR_ARG;
+    const int32_t frame_offsets[2] = {0, n_points};
+    return voxelize_batch_impl(points, nullptr, frame_offsets, 1, c, vsize_xyz, range_xyz, max_points, max_voxels, voxels, coords,
+                               num_points, mean_features, n_voxels, workspace, workspace_bytes, nullptr, 0, 0, 0, coord_cols, batch_idx,
+                               false, stream);
 }
 
 extern "C" int cpd_voxelize_batch(const float *points, const int32_t *frame_offsets, int n_frames, int c,
@@ -811,7 +659,7 @@ extern "C" int cpd_voxelize_batch(const float *points, const int32_t *frame_offs
                                   float *voxels, int32_t *coords, int32_t *num_points, float *mean_features,
                                   int32_t *n_voxels, void *workspace, size_t workspace_bytes, cpd_stream_t stream) {
     return voxelize_batch_impl(points, nullptr, frame_offsets, n_frames, c, vsize_xyz, range_xyz, max_points, max_voxels, voxels, coords,
-                               num_points, mean_features, n_voxels, workspace, workspace_bytes, nullptr, 0, 0, 0, stream);
+                               num_points, mean_features, n_voxels, workspace, workspace_bytes, nullptr, 0, 0, 0, 4, 0, true, stream);
 }
 
 extern "C" int cpd_voxelize_batch_index(const float *points, const int32_t *frame_offsets, int n_frames, int c,
@@ -821,7 +669,7 @@ extern "C" int cpd_voxelize_batch_index(const float *points, const int32_t *fram
                                         size_t index_bytes, int z_extra, cpd_stream_t stream) {
     if (!index) return CPD_ERR_ARG;
     return voxelize_batch_impl(points, nullptr, frame_offsets, n_frames, c, vsize_xyz, range_xyz, max_points, max_voxels, voxels, coords,
-                               num_points, mean_features, n_voxels, workspace, workspace_bytes, index, index_bytes, z_extra, 0, stream);
+                               num_points, mean_features, n_voxels, workspace, workspace_bytes, index, index_bytes, z_extra, 0, 4, 0, true, stream);
 }
 
 extern "C" int cpd_voxelize_batch_canonical(const float *points, const int32_t *frame_offsets, int n_frames, int c,
@@ -831,7 +679,7 @@ extern "C" int cpd_voxelize_batch_canonical(const float *points, const int32_t *
                                             size_t index_bytes, int z_extra, cpd_stream_t stream) {
     if (!index) return CPD_ERR_ARG;
     return voxelize_batch_impl(points, nullptr, frame_offsets, n_frames, c, vsize_xyz, range_xyz, max_points, max_voxels, voxels, coords,
-                               num_points, mean_features, n_voxels, workspace, workspace_bytes, index, index_bytes, z_extra, 1, stream);
+                               num_points, mean_features, n_voxels, workspace, workspace_bytes, index, index_bytes, z_extra, 1, 4, 0, true, stream);
 }
 
 // The frames' point lists as they lie -- one device pointer per frame (a HOST array of n_frames pointers; frame f holds
@@ -845,5 +693,5 @@ extern "C" int cpd_voxelize_batch_frames(const float *const *frame_points, const
     if (!frame_points || (canonical && !index)) return CPD_ERR_ARG;
     return voxelize_batch_impl(nullptr, frame_points, frame_offsets, n_frames, c, vsize_xyz, range_xyz, max_points, max_voxels, voxels, coords,
                                num_points, mean_features, n_voxels, workspace, workspace_bytes, index, index ? index_bytes : 0,
-                               index ? z_extra : 0, canonical, stream);
+                               index ? z_extra : 0, canonical, 4, 0, true, stream);
 }

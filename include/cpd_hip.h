@@ -51,9 +51,12 @@ int cpd_last_hip_error(void); /* hipError_t of the last CPD_ERR_LAUNCH on this t
  */
 /* grid = round((hi-lo)/vs) in fp32, returned (z,y,x). HOST in, HOST out. */
 int cpd_voxel_grid_size(const float vsize_xyz[3], const float range_xyz[6], int32_t grid_zyx[3]);
+/* = cpd_voxelize_batch_workspace_bytes(n_points, 1, ...); 0 for bad arguments or a grid of >= 2^31 cells. */
 size_t cpd_voxelize_workspace_bytes(int n_points, int max_points, int max_voxels,
                                     const float vsize_xyz[3], const float range_xyz[6]);
-/* points [n_points, c] f32 (x,y,z,...). Outputs sized for cap = min(max_voxels, n_points) rows:
+/* One frame: cpd_voxelize_batch (below) with n_frames = 1, the same kernels. What differs is the boundary: coord_cols and
+ * batch_idx shape the coordinates, and n_voxels is ONE int (nothing is written behind it).
+ * points [n_points, c] f32 (x,y,z,...). Outputs sized for cap = min(max_voxels, n_points) rows:
  *   voxels        [cap, max_points, c] f32, zero padded            (may be NULL)
  *   coords        [cap, coord_cols] i32; coord_cols 3 -> (z,y,x), 4 -> (batch_idx,z,y,x)
  *                 (the pad of collate_batch, cpd/datasets/dataset.py:264)

@@ -31,6 +31,19 @@ def check(oracle, points, cfg, P=None, maxv=None):
     return c0.shape[0]
 
 
+def check_frame_against_oracle(oracle, points, cfg, P, maxv, b, voxels, coords, num, mean):
+    """one frame's rows of a batched call against the serial CPU oracle (the same comparison as `check`)"""
+    v0, c0, n0 = oracle.voxelize(points, cfg["voxel_size"], cfg["point_cloud_range"], P, maxv)
+    assert coords.shape[0] == c0.shape[0]
+    c = coords.cpu().numpy()
+    assert (c[:, 0] == b).all()
+    np.testing.assert_array_equal(c[:, 1:], c0)
+    np.testing.assert_array_equal(num.cpu().numpy(), n0)
+    np.testing.assert_array_equal(voxels.cpu().numpy(), v0)
+    if len(n0):
+        np.testing.assert_allclose(mean.cpu().numpy(), oracle.mean_vfe(v0, n0), rtol=1e-6, atol=1e-6)
+
+
 def test_waymo_160k_bit_exact(oracle, hip):
     m = check(oracle, waymo_cloud(0), WAYMO)
     assert m > 50000
@@ -78,9 +91,9 @@ def test_batch_column_and_voxel_boundaries(oracle, hip):
 
 
 @pytest.mark.parametrize("max_voxels", [1000000, 900])
-def test_batched_voxelizer_equals_per_frame(hip, max_voxels):
-    """cpd_voxelize_batch == cpd_voxelize frame by frame (itself bit-exact vs the oracle): same rows, same
-    order, same per-frame max_voxels cap, including an empty frame in the middle."""
+def test_batched_voxelizer_equals_per_frame(oracle, hip, max_voxels):
+    """cpd_voxelize_batch == cpd_voxelize frame by frame: same rows, same order, same per-frame max_voxels cap, including an
+    empty frame in the middle. The one-frame call runs the batch's kernels, so every frame is held against the oracle as well."""
     import torch
     from cpd_amd import ops
     from cpd_amd.synthetic import WAYMO, waymo_cloud
@@ -97,6 +110,8 @@ def test_batched_voxelizer_equals_per_frame(hip, max_voxels):
         assert counts[b] == k
         assert torch.equal(coords[row:row + k], c1) and torch.equal(num[row:row + k], n1)
         assert torch.equal(voxels[row:row + k], v1) and torch.equal(mean[row:row + k], m1)
+        check_frame_against_oracle(oracle, frames[b], WAYMO, 5, max_voxels, b, voxels[row:row + k], coords[row:row + k],
+                                   num[row:row + k], mean[row:row + k])
         row += k
     assert counts[len(frames)] == row
 
@@ -168,10 +183,10 @@ def test_batched_voxelizer_builds_the_level0_site_index(oracle, hip):
         np.testing.assert_array_equal(got.cpu().numpy(), oracle.subm_rulebook(coords.cpu().numpy(), len(clouds), shape, [3, 3, 3]))
 
 
-def test_batched_voxelizer_beyond_2_to_31_cells(hip):
+def test_batched_voxelizer_beyond_2_to_31_cells(oracle, hip):
     """30 frames of the Waymo grid = 2.8e9 cells: bitmap positions are formed in 64 bits (frame x cells-per-frame + cell). Every
-    frame of the batch must equal the per-frame voxelizer, the last ones (positions above 2^31) in particular, and the index
-    built in place must answer lookups like one built from the coordinates."""
+    frame of the batch must equal the per-frame voxelizer AND the oracle, the last ones (positions above 2^31) in particular, and
+    the index built in place must answer lookups like one built from the coordinates."""
     import torch
     from cpd_amd import ops
     from cpd_amd.synthetic import WAYMO, waymo_cloud
@@ -191,6 +206,8 @@ def test_batched_voxelizer_beyond_2_to_31_cells(hip):
         assert counts[b] == k
         assert torch.equal(coords[row:row + k], c1) and torch.equal(num[row:row + k], n1)
         assert torch.equal(voxels[row:row + k], v1) and torch.equal(mean[row:row + k], m1)
+        check_frame_against_oracle(oracle, dev[b].cpu().numpy(), WAYMO, 5, 1000000, b, voxels[row:row + k], coords[row:row + k],
+                                   num[row:row + k], mean[row:row + k])
     total = int(counts[nf])
     cc = coords[:total].contiguous()
     shape = [g[0] + 1, g[1], g[2]]

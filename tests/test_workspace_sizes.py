@@ -6,7 +6,9 @@ layouts were given one definition each (recorded from a build of that commit, no
 smallest legal shape, a shape at which a piece's raw size is a whole number of 256-byte units, the same shape with one more element,
 a refused shape (0 or 256, as the query has always answered; a few queries clamp a bad count to 1 instead), and for the queries
 with a scan spine a count on either side of one 4096-item scan tile. The two row-order queries are newer than that recording:
-their values are the expressions their hosts used to compute themselves."""
+their values are the expressions their hosts used to compute themselves. cpd_voxelize has since become the one-frame call of the
+batched voxelizer: its five positive rows are what cpd_voxelize_batch_workspace_bytes(n, 1, ...) answered for the same arguments in
+the library BEFORE that change (the per-frame tail of the batch layout is always there now)."""
 import pytest
 
 from cpd_amd import _lib
@@ -15,8 +17,8 @@ VS, RG = (1.0, 1.0, 1.0), (0.0, 0.0, 0.0, 8.0, 8.0, 4.0)       # voxel size and 
 
 SIZES = {
     "cpd_voxelize_workspace_bytes": [
-        ((0, 1, 1, VS, RG), 2816), ((64, 1, 64, VS, RG), 2816), ((65, 1, 65, VS, RG), 4352), ((4096, 5, 100, VS, RG), 69376),
-        ((4097, 5, 100, VS, RG), 70400), ((-1, 1, 1, VS, RG), 0), ((1, 0, 1, VS, RG), 0),
+        ((0, 1, 1, VS, RG), 3584), ((64, 1, 64, VS, RG), 3584), ((65, 1, 65, VS, RG), 5120), ((4096, 5, 100, VS, RG), 70144),
+        ((4097, 5, 100, VS, RG), 71168), ((-1, 1, 1, VS, RG), 0), ((1, 0, 1, VS, RG), 0),
     ],
     "cpd_voxelize_batch_workspace_bytes": [
         ((0, 1, 1, 1, VS, RG), 3584), ((64, 1, 1, 64, VS, RG), 3584), ((65, 1, 1, 65, VS, RG), 5120),
@@ -140,6 +142,13 @@ SIZES["cpd_order_rows_by_taps_workspace_bytes"] = [((n,), max(n, 1) * 4) for n i
 
 def test_every_workspace_query_is_pinned():
     assert sorted(SIZES) == sorted(n for n in _lib.SIGNATURES if n.endswith("_workspace_bytes"))
+
+
+def test_one_frame_voxelizer_query_is_the_batch_query_of_one_frame():
+    one, batch = _lib.lib().cpd_voxelize_workspace_bytes, _lib.lib().cpd_voxelize_batch_workspace_bytes
+    for (n, p, v, vs, rg), want in SIZES["cpd_voxelize_workspace_bytes"]:
+        if want:
+            assert one(n, p, v, _lib.farr(vs), _lib.farr(rg)) == batch(n, 1, p, v, _lib.farr(vs), _lib.farr(rg)) == want
 
 
 @pytest.mark.parametrize("name", sorted(SIZES))
