@@ -117,6 +117,7 @@ SIGNATURES = {
     "cpd_nearest_bev_iou": (_I, [_VP, _I, _VP, _I, _VP, _VP]),
     "cpd_anchor_assign_workspace_bytes": (_SZ, [_I, _I]),
     "cpd_anchor_assign": (_I, [_VP, _I, _VP, _I, _VP, _F, _F, _I, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "cpd_anchor_assign_batch": (_I, [_VP, _I, _I3, _I3, _I3, _FP, _FP, _I, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "cpd_anchor_decode": (_I, [_VP, _VP, _VP, _I, _I, _I, _F, _F, _VP, _VP]),
     "cpd_points_in_boxes_mask": (_I, [_VP, _I, _VP, _I, _I, _VP, _VP]),
     "cpd_crop_boxes_workspace_bytes": (_SZ, [_I]),

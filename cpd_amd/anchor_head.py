@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import layer_table, ops
-from ._lib import check, farr, lib, ptr, stream
+from ._lib import check, farr, iarr, lib, ptr, stream
 
 
 class AnchorGenerator:
@@ -79,8 +79,67 @@ def assign_targets_single(anchors, gt_boxes, gt_classes, matched_threshold=0.6, 
     return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights, "gt_ious": ious}
 
 
+MAX_ANCHOR_SETS, MAX_BATCH_GT = 8, 2048                            # cpd_anchor_assign_batch's limits
+
+
+def _batch_assignable(all_anchors, gt_boxes_with_classes, class_names, anchor_class_names):
+    """Whether cpd_anchor_assign_batch covers this call: float32 device tensors, its limits, every class named once, anchor
+    sets of one feature_map_size product. Shapes and dtypes only -- nothing here reads a tensor."""
+    gt = gt_boxes_with_classes
+    if not (isinstance(all_anchors, (list, tuple)) and 1 <= len(all_anchors) <= MAX_ANCHOR_SETS and
+            len(all_anchors) == len(anchor_class_names)):
+        return False
+    if not (torch.is_tensor(gt) and gt.is_cuda and gt.dtype == torch.float32 and gt.dim() == 3 and gt.shape[0] >= 1 and
+            gt.shape[2] >= 8 and gt.shape[1] <= MAX_BATCH_GT):
+        return False
+    if len(set(class_names)) != len(class_names) or len(set(anchor_class_names)) != len(anchor_class_names) or \
+            any(name not in class_names for name in anchor_class_names):
+        return False
+    outer = set()
+    for a in all_anchors:
+        if not (torch.is_tensor(a) and a.device == gt.device and a.dtype == torch.float32 and a.dim() >= 3 and a.shape[-1] == 7 and
+                a.numel() > 0):
+            return False
+        outer.add(a.shape[0] * a.shape[1])
+    return len(outer) == 1
+
+
+def assign_targets_batch(all_anchors, gt_boxes_with_classes, class_names, anchor_class_names, matched, unmatched,
+                         norm_by_num_examples=False):
+    """AxisAlignedTargetAssigner.assign_targets for the whole batch in one cpd_anchor_assign_batch call (at most three launches and
+    two memsets, no host read-back): all_anchors = the per-class anchor tensors (feature_map_size = shape[:2], as in the reference),
+    gt_boxes_with_classes (B, M, >= 8) float32 on the device, matched / unmatched = thresholds by class name. Returns the four keys
+    of assign_targets in its layout, plus gt_max_iou (B, M) -- per row the largest IoU an anchor of its class attains -- and
+    n_examples (B, sets) -- labels >= 0 per frame and set."""
+    gt = gt_boxes_with_classes.contiguous()
+    B, M, ld = gt.shape
+    dev = gt.device
+    flat = torch.cat([a.reshape(-1, 7) for a in all_anchors], dim=0)
+    set_n = [a.numel() // 7 for a in all_anchors]
+    set_inner = [n // (a.shape[0] * a.shape[1]) for n, a in zip(set_n, all_anchors)]
+    set_class = [class_names.index(name) + 1 for name in anchor_class_names]
+    n = sum(set_n)
+    labels = torch.empty((B, n), dtype=torch.int32, device=dev)
+    targets = torch.empty((B, n, 7), dtype=torch.float32, device=dev)
+    weights = torch.empty((B, n), dtype=torch.float32, device=dev)
+    ious = torch.empty((B, n), dtype=torch.float32, device=dev)
+    gt_max = torch.empty((B, M), dtype=torch.float32, device=dev)
+    n_examples = torch.empty((B, len(set_n)), dtype=torch.int32, device=dev)
+    check(lib().cpd_anchor_assign_batch(ptr(flat), len(set_n), iarr(set_n), iarr(set_inner), iarr(set_class),
+                                        farr([matched[name] for name in anchor_class_names]),
+                                        farr([unmatched[name] for name in anchor_class_names]), len(class_names), ptr(gt), B, M, ld,
+                                        int(bool(norm_by_num_examples)), ptr(labels), ptr(targets), ptr(weights), ptr(ious),
+                                        ptr(gt_max), ptr(n_examples), stream()), "cpd_anchor_assign_batch")
+    return {"box_cls_labels": labels, "box_reg_targets": targets, "reg_weights": weights, "gt_ious": ious,
+            "gt_max_iou": gt_max, "n_examples": n_examples}
+
+
 class AxisAlignedTargetAssigner:
-    """assign_targets with the reference's output layout (use_multihead = False, match_height = False, no sampling)."""
+    """assign_targets with the reference's output layout (use_multihead = False, match_height = False, no sampling).
+
+    `fused` (default False; set_fused_anchor_targets flips it on a whole model): float32 device inputs within
+    cpd_anchor_assign_batch's limits, with every class named once, take assign_targets_batch -- the same four keys, bit for bit,
+    without the host loop and its read-backs. Anything else takes the loop."""
 
     def __init__(self, anchor_generator_cfg, class_names, norm_by_num_examples=False):
         self.class_names = list(class_names)
@@ -88,8 +147,13 @@ class AxisAlignedTargetAssigner:
         self.matched = {c["class_name"]: c["matched_threshold"] for c in anchor_generator_cfg}
         self.unmatched = {c["class_name"]: c["unmatched_threshold"] for c in anchor_generator_cfg}
         self.norm_by_num_examples = norm_by_num_examples
+        self.fused = False
 
     def assign_targets(self, all_anchors, gt_boxes_with_classes):
+        if self.fused and _batch_assignable(all_anchors, gt_boxes_with_classes, self.class_names, self.anchor_class_names):
+            t = assign_targets_batch(all_anchors, gt_boxes_with_classes, self.class_names, self.anchor_class_names, self.matched,
+                                     self.unmatched, self.norm_by_num_examples)
+            return {k: t[k] for k in ("box_cls_labels", "box_reg_targets", "reg_weights", "gt_ious")}
         out = {"box_cls_labels": [], "box_reg_targets": [], "reg_weights": [], "gt_ious": []}
         gt_classes = gt_boxes_with_classes[:, :, -1]
         gt_boxes = gt_boxes_with_classes[:, :, :-1]
@@ -386,6 +450,20 @@ class AnchorHeadSingle(torch.nn.Module):
         if not self.training or self.predict_boxes_when_training:
             self._predict(data_dict, cls_preds, box_preds, dir_preds)
         return data_dict
+
+
+def set_fused_anchor_targets(model, on=True):
+    """Flip `fused` on the AxisAlignedTargetAssigner of every anchor head in `model` (AnchorHeadSingle and AnchorHeadSingleV2; the
+    lazy target_assigner is built for it); returns how many assigners it flipped. A head without a TARGET_ASSIGNER_CONFIG, or with
+    the ATSS assigner, has nothing to flip."""
+    n = 0
+    for mod in model.modules():
+        if isinstance(mod, AnchorHeadSingle) and "TARGET_ASSIGNER_CONFIG" in mod.model_cfg:
+            assigner = mod.target_assigner
+            if isinstance(assigner, AxisAlignedTargetAssigner):
+                assigner.fused = bool(on)
+                n += 1
+    return n
 
 
 def get_layer(dim, out_dim, init=None):

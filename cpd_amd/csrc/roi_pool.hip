@@ -568,6 +568,38 @@ __global__ void __launch_bounds__(256) assign_pass1_kernel(const float *__restri
     amax_idx[i] = bj;
 }
 
+// What follows the IoUs, shared by cpd_anchor_assign and cpd_anchor_assign_batch (axis_aligned_target_assigner.py:178-243 with
+// POS_FRACTION < 0). The label of an anchor whose best row has class `cls`: forced or matched -> cls, below unmatched ->
+// background, forced again (l.183-216).
+__device__ __forceinline__ int32_t assign_label(bool forced, float iou, int32_t cls, float matched, float unmatched) {
+    int32_t lab = -1;
+    if (forced || iou >= matched) lab = cls;
+    if (iou < unmatched) lab = 0;
+    if (forced) lab = cls;
+    return lab;
+}
+// ResidualCoder.encode_torch of box g against anchor an for a positive label, zeros otherwise (g is not read then)
+__device__ __forceinline__ void assign_encode(int32_t lab, const float *__restrict__ g, const float *__restrict__ an,
+                                              float *__restrict__ o) {
+    if (lab > 0) {
+        const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
+        const float dxg = fmaxf(g[3], 1e-5f), dyg = fmaxf(g[4], 1e-5f), dzg = fmaxf(g[5], 1e-5f);
+        const float diag = sqrtf(__fadd_rn(__fmul_rn(dxa, dxa), __fmul_rn(dya, dya)));
+        o[0] = div_rn(__fsub_rn(g[0], an[0]), diag);
+        o[1] = div_rn(__fsub_rn(g[1], an[1]), diag);
+        o[2] = div_rn(__fsub_rn(g[2], an[2]), dza);
+        o[3] = logf(div_rn(dxg, dxa)); o[4] = logf(div_rn(dyg, dya)); o[5] = logf(div_rn(dzg, dza));
+        o[6] = __fsub_rn(g[6], an[6]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) o[k] = 0.f;
+    }
+}
+// reg_weights (l.232-240): 1 on positives, or 1 / max(n_examples, 1) under norm_by_num_examples
+__device__ __forceinline__ float assign_weight(int32_t lab, int n_examples, int norm) {
+    return lab > 0 ? (norm ? 1.0f / (float)(n_examples > 1 ? n_examples : 1) : 1.0f) : 0.f;
+}
+
 // Pass 2: force-match anchors that attain some GT's maximum (exact float equality, l.178), thresholds,
 // background, regression targets (ResidualCoder.encode_torch) -- axis_aligned_target_assigner.py:178-243
 // with POS_FRACTION < 0.
@@ -593,27 +625,10 @@ __global__ void __launch_bounds__(256) assign_pass2_kernel(const float *__restri
     for (int j = 0; j < m && !forced; ++j) forced = iou_normal(a, sgt[j]) == sgm[j];
     const float iou = amax_iou[i];
     const int j = amax_idx[i];
-    int32_t lab = -1;
-    if (forced || iou >= matched) lab = gt_classes[j];
-    if (iou < unmatched) lab = 0;
-    if (forced) lab = gt_classes[j];
+    const int32_t lab = assign_label(forced, iou, gt_classes[j], matched, unmatched);
     labels[i] = lab;
     gt_ious[i] = iou;
-    float *o = targets + 7 * (size_t)i;
-    if (lab > 0) {
-        const float *g = gt + 7 * (size_t)j;
-        const float dxa = fmaxf(an[3], 1e-5f), dya = fmaxf(an[4], 1e-5f), dza = fmaxf(an[5], 1e-5f);
-        const float dxg = fmaxf(g[3], 1e-5f), dyg = fmaxf(g[4], 1e-5f), dzg = fmaxf(g[5], 1e-5f);
-        const float diag = sqrtf(__fadd_rn(__fmul_rn(dxa, dxa), __fmul_rn(dya, dya)));
-        o[0] = div_rn(__fsub_rn(g[0], an[0]), diag);
-        o[1] = div_rn(__fsub_rn(g[1], an[1]), diag);
-        o[2] = div_rn(__fsub_rn(g[2], an[2]), dza);
-        o[3] = logf(div_rn(dxg, dxa)); o[4] = logf(div_rn(dyg, dya)); o[5] = logf(div_rn(dzg, dza));
-        o[6] = __fsub_rn(g[6], an[6]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 7; ++k) o[k] = 0.f;
-    }
+    assign_encode(lab, gt + 7 * (size_t)j, an, targets + 7 * (size_t)i);
     if (lab >= 0) atomicAdd(n_examples, 1);
 }
 
@@ -621,8 +636,174 @@ __global__ void __launch_bounds__(256) assign_weights_kernel(int n, const int32_
                                                              int norm, float *__restrict__ w) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int ne = *n_examples;
-    w[i] = labels[i] > 0 ? (norm ? 1.0f / (float)(ne > 1 ? ne : 1) : 1.0f) : 0.f;
+    w[i] = assign_weight(labels[i], *n_examples, norm);
+}
+
+// ---- the assigner for a whole batch: every (frame, anchor set) pair in one grid --------------------------------------------
+// Same arithmetic as the two kernels above, through the same device functions; what differs is where the rows come from (each
+// block trims and filters its frame's gt_boxes itself) and where the results go (the reference's concatenated layout).
+constexpr int ASSIGN_MAX_SETS = 8;
+struct AssignSets {
+    int n_sets, num_classes, sum_inner, total_n;
+    int n[ASSIGN_MAX_SETS], inner[ASSIGN_MAX_SETS], cls[ASSIGN_MAX_SETS];
+    int first[ASSIGN_MAX_SETS];                                   // the set's first anchor in the concatenated anchors
+    int col0[ASSIGN_MAX_SETS];                                    // inner[0] + ... + inner[s - 1]
+    float matched[ASSIGN_MAX_SETS], unmatched[ASSIGN_MAX_SETS];
+};
+
+// dynamic LDS of the batched kernels, every piece a multiple of 16 bytes (m rounded up to 8 rows): the rows' aligned boxes,
+// their maxima (pass 1: float bits under construction, pass 2: the finished values), their row numbers in the frame, scratch
+struct AssignLds { float4 *box; float *gmax; unsigned short *row; int *scratch; };
+__host__ __device__ __forceinline__ size_t assign_lds_rows(int m) { return ((size_t)m + 7) & ~(size_t)7; }
+static size_t assign_lds_bytes(int m) { return assign_lds_rows(m) * 22 + 64; }
+__device__ __forceinline__ AssignLds assign_lds(unsigned char *base, int m) {
+    const size_t r = assign_lds_rows(m);
+    AssignLds l;
+    l.box = reinterpret_cast<float4 *>(base);
+    l.gmax = reinterpret_cast<float *>(base + r * 16);
+    l.row = reinterpret_cast<unsigned short *>(base + r * 20);
+    l.scratch = reinterpret_cast<int *>(base + r * 22);
+    return l;
+}
+
+// gt_boxes_with_classes[:, :, -1] as the index the host loop makes of it: class_names[int(c) - 1], where Python wraps an index
+// below zero -- class id 0 (a padding row that survived the trim) lands in the LAST class
+__device__ __forceinline__ int assign_row_class(const float *row, int ld, int num_classes) {
+    const int c = (int)row[ld - 1];
+    return c <= 0 ? c + num_classes : c;
+}
+
+// One frame's rows of one class, in their order, into LDS (256 threads, all of them): rows 0 .. last with a non-zero box column
+// are kept (at least row 0), a thread owns a run of consecutive rows, a block scan of the per-thread counts gives each run its
+// place. gmax_bits == nullptr: the maxima start at 0; else they are read (0 -> -1: a row nothing overlaps matches nothing).
+// Returns the number of rows staged; ends in a barrier.
+__device__ int assign_stage_rows(const float *__restrict__ gt, int m, int ld, int set_class, int num_classes,
+                                 const int32_t *__restrict__ gmax_bits, const AssignLds &l) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) l.scratch[0] = -1;
+    __syncthreads();
+    int last = -1;
+    for (int j = tid; j < m; j += 256) {
+        const float *r = gt + (size_t)j * ld;
+        bool nz = false;
+        for (int c = 0; c < ld - 1; ++c) nz |= r[c] != 0.f;
+        if (nz) last = j;
+    }
+    if (last >= 0) atomicMax(&l.scratch[0], last);
+    __syncthreads();
+    const int cnt = min(m, max(l.scratch[0] + 1, 1));
+    const int per = (cnt + 255) / 256, j0 = min(tid * per, cnt), j1 = min(j0 + per, cnt);
+    int mine = 0;
+    for (int j = j0; j < j1; ++j) mine += assign_row_class(gt + (size_t)j * ld, ld, num_classes) == set_class;
+    int incl = mine;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) l.scratch[1 + wave] = incl;
+    __syncthreads();
+    int at = incl - mine, total = 0;
+    for (int w = 0; w < 4; ++w) {
+        const int t = l.scratch[1 + w];
+        if (w < wave) at += t;
+        total += t;
+    }
+    for (int j = j0; j < j1; ++j) {
+        const float *r = gt + (size_t)j * ld;
+        if (assign_row_class(r, ld, num_classes) != set_class) continue;
+        l.box[at] = aligned_bev(r);
+        l.row[at] = (unsigned short)j;
+        const int bits = gmax_bits ? gmax_bits[j] : 0;
+        l.gmax[at] = gmax_bits && bits == 0 ? -1.f : __int_as_float(bits);
+        ++at;
+    }
+    __syncthreads();
+    return total;
+}
+
+// Pass 1, grid (anchor blocks of the largest set, frame x set): gt_max_iou[frame][row] = the largest IoU any anchor of the row's
+// set attains, as float bits (IoUs are >= 0, so integer order is float order); a block folds its anchors in LDS first.
+__global__ void __launch_bounds__(256) assign_batch_pass1_kernel(const float *__restrict__ anchors, AssignSets sets,
+                                                                 const float *__restrict__ gt, int m, int ld,
+                                                                 int32_t *__restrict__ gmax_bits) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char assign_smem[];
+    const int s = blockIdx.y % sets.n_sets, b = blockIdx.y / sets.n_sets, n = sets.n[s];
+    if ((int)blockIdx.x * 256 >= n) return;
+    const AssignLds l = assign_lds(assign_smem, m);
+    const int k = assign_stage_rows(gt + (size_t)b * m * ld, m, ld, sets.cls[s], sets.num_classes, nullptr, l);
+    if (k == 0) return;
+    int *smax = reinterpret_cast<int *>(l.gmax);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const float4 a = aligned_bev(anchors + 7 * ((size_t)sets.first[s] + i));
+        for (int j = 0; j < k; ++j) {
+            const float v = iou_normal(a, l.box[j]);
+            if (v > 0.f) atomicMax(&smax[j], __float_as_int(v));
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < k; j += 256)
+        if (smax[j] > 0) atomicMax(&gmax_bits[(size_t)b * m + l.row[j]], smax[j]);
+}
+
+// Pass 2, same grid: per anchor the maximum, its first row and the forced test in one loop over the rows, then the label, the
+// IoU, the targets and (without the norm) the weight at the anchor's place in the frame's row; n_examples[frame][set] counts
+// labels >= 0, one add per wave. A set without rows is background.
+__global__ void __launch_bounds__(256) assign_batch_pass2_kernel(const float *__restrict__ anchors, AssignSets sets,
+                                                                 const float *__restrict__ gt, int m, int ld,
+                                                                 const int32_t *__restrict__ gmax_bits, int norm,
+                                                                 int32_t *__restrict__ labels, float *__restrict__ targets,
+                                                                 float *__restrict__ weights, float *__restrict__ gt_ious,
+                                                                 int32_t *__restrict__ n_examples) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char assign_smem[];
+    const int s = blockIdx.y % sets.n_sets, b = blockIdx.y / sets.n_sets, n = sets.n[s];
+    if ((int)blockIdx.x * 256 >= n) return;
+    const AssignLds l = assign_lds(assign_smem, m);
+    const float *fgt = gt + (size_t)b * m * ld;
+    const int k = assign_stage_rows(fgt, m, ld, sets.cls[s], sets.num_classes, gmax_bits + (size_t)b * m, l);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool example = false;
+    if (i < n) {
+        const float *an = anchors + 7 * ((size_t)sets.first[s] + i);
+        const float *g = an;                                      // not read unless the label is positive
+        float iou = 0.f;
+        int32_t lab = 0;
+        if (k > 0) {
+            const float4 a = aligned_bev(an);
+            float best = -1.f;
+            int bj = 0;
+            bool forced = false;
+            for (int j = 0; j < k; ++j) {
+                const float v = iou_normal(a, l.box[j]);
+                if (v > best) { best = v; bj = j; }               // first maximum, like numpy argmax
+                forced |= v == l.gmax[j];
+            }
+            g = fgt + (size_t)l.row[bj] * ld;
+            iou = best;
+            lab = assign_label(forced, iou, (int32_t)g[ld - 1], sets.matched[s], sets.unmatched[s]);
+        }
+        const int inner = sets.inner[s];
+        const size_t o = (size_t)b * sets.total_n + (size_t)(i / inner) * sets.sum_inner + sets.col0[s] + i % inner;
+        labels[o] = lab;
+        gt_ious[o] = iou;
+        assign_encode(lab, g, an, targets + 7 * o);
+        if (!norm) weights[o] = assign_weight(lab, 0, 0);
+        example = lab >= 0;
+    }
+    const unsigned long long votes = __ballot(example);
+    if ((threadIdx.x & 63) == 0 && votes) atomicAdd(&n_examples[b * sets.n_sets + s], __popcll(votes));
+}
+
+// norm_by_num_examples: the weights need the finished counts
+__global__ void __launch_bounds__(256) assign_batch_weights_kernel(AssignSets sets, long long total,
+                                                                   const int32_t *__restrict__ labels,
+                                                                   const int32_t *__restrict__ n_examples, float *__restrict__ w) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / sets.total_n), q = (int)(i % sets.total_n) % sets.sum_inner;
+    int s = 0;
+    while (s + 1 < sets.n_sets && q >= sets.col0[s + 1]) ++s;
+    w[i] = assign_weight(labels[i], n_examples[b * sets.n_sets + s], 1);
 }
 
 // ResidualCoder.decode_torch + direction classifier (anchor_head_template.py:363-376)
@@ -703,6 +884,66 @@ extern "C" int cpd_anchor_assign(const float *anchors, int n, const float *gt, i
     assign_pass2_kernel<<<nb, 256, (size_t)m * 20, s>>>(anchors, n, gt, m, gt_classes, matched_thr, unmatched_thr, amax_iou, amax_idx,
                                                        gmax_bits, labels, bbox_targets, gt_ious, n_examples);
     assign_weights_kernel<<<nb, 256, 0, s>>>(n, labels, n_examples, norm_by_num_examples, reg_weights);
+    return cpd_check_launch();
+}
+
+extern "C" int cpd_anchor_assign_batch(const float *anchors, int n_sets, const int32_t set_n[], const int32_t set_inner[],
+                                       const int32_t set_class[], const float set_matched[], const float set_unmatched[],
+                                       int num_classes, const float *gt_boxes, int batch, int m, int gt_ld,
+                                       int norm_by_num_examples, int32_t *labels, float *bbox_targets, float *reg_weights,
+                                       float *gt_ious, float *gt_max_iou, int32_t *n_examples, cpd_stream_t st) {
+    if (n_sets < 1 || n_sets > ASSIGN_MAX_SETS || !set_n || !set_inner || !set_class || !set_matched || !set_unmatched ||
+        num_classes < 1 || batch < 0 || m < 0 || m > 2048 || gt_ld < 8)
+        return CPD_ERR_ARG;
+    AssignSets sets;
+    sets.n_sets = n_sets;
+    sets.num_classes = num_classes;
+    long long total = 0;
+    int sum_inner = 0, max_n = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        if (set_n[s] < 0 || set_inner[s] < 1 || set_n[s] % set_inner[s] || set_class[s] < 1 || set_class[s] > num_classes ||
+            set_n[s] / set_inner[s] != set_n[0] / set_inner[0])
+            return CPD_ERR_ARG;
+        for (int t = 0; t < s; ++t)
+            if (set_class[t] == set_class[s]) return CPD_ERR_ARG;  // a row belongs to one set: gt_max_iou has one slot per row
+        sets.n[s] = set_n[s];
+        sets.inner[s] = set_inner[s];
+        sets.cls[s] = set_class[s];
+        sets.first[s] = (int)total;
+        sets.col0[s] = sum_inner;
+        sets.matched[s] = set_matched[s];
+        sets.unmatched[s] = set_unmatched[s];
+        total += set_n[s];
+        sum_inner += set_inner[s];
+        max_n = set_n[s] > max_n ? set_n[s] : max_n;
+        if (total > 0x7fffffffLL / 7) return CPD_ERR_ARG;
+    }
+    for (int s = n_sets; s < ASSIGN_MAX_SETS; ++s) {
+        sets.n[s] = sets.cls[s] = sets.first[s] = sets.col0[s] = 0;
+        sets.inner[s] = 1;
+        sets.matched[s] = sets.unmatched[s] = 0.f;
+    }
+    sets.sum_inner = sum_inner;
+    sets.total_n = (int)total;
+    if ((long long)batch * n_sets > 65535 || (long long)batch * total > (1LL << 38))   // frame x set is the grid's y
+        return CPD_ERR_ARG;
+    if (batch == 0) return CPD_OK;
+    if (!n_examples || (m > 0 && (!gt_boxes || !gt_max_iou)) ||
+        (total > 0 && (!anchors || !labels || !bbox_targets || !reg_weights || !gt_ious)))
+        return CPD_ERR_ARG;
+    hipStream_t s = cpd_s(st);
+    if (m > 0) CPD_HIP_TRY(hipMemsetAsync(gt_max_iou, 0, (size_t)batch * m * 4, s));
+    CPD_HIP_TRY(hipMemsetAsync(n_examples, 0, (size_t)batch * n_sets * 4, s));
+    if (total == 0) return CPD_OK;
+    const dim3 grid(cpd_div_up(max_n, 256), batch * n_sets);
+    const size_t lds = assign_lds_bytes(m);
+    int32_t *gmax_bits = reinterpret_cast<int32_t *>(gt_max_iou);
+    if (m > 0) assign_batch_pass1_kernel<<<grid, 256, lds, s>>>(anchors, sets, gt_boxes, m, gt_ld, gmax_bits);
+    assign_batch_pass2_kernel<<<grid, 256, lds, s>>>(anchors, sets, gt_boxes, m, gt_ld, gmax_bits, norm_by_num_examples, labels,
+                                                    bbox_targets, reg_weights, gt_ious, n_examples);
+    if (norm_by_num_examples)
+        assign_batch_weights_kernel<<<cpd_div_up((long long)batch * total, 256), 256, 0, s>>>(sets, (long long)batch * total, labels,
+                                                                                             n_examples, reg_weights);
     return cpd_check_launch();
 }
 

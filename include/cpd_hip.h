@@ -997,6 +997,24 @@ int cpd_anchor_assign(const float *anchors, int n, const float *gt_boxes, int m,
                       float matched_threshold, float unmatched_threshold, int norm_by_num_examples,
                       int32_t *labels, float *bbox_targets, float *reg_weights, float *gt_ious,
                       void *workspace, size_t workspace_bytes, cpd_stream_t stream);
+/* AxisAlignedTargetAssigner.assign_targets (l.46-151) for a whole batch: every (frame, anchor set) pair in at most three launches
+ * and two memsets, with cpd_anchor_assign's arithmetic per pair and the reference's output layout. anchors [sum(set_n)][7], the
+ * sets one after another (device); the five set_* arrays are HOST arrays of n_sets <= 8 entries: anchors per set, anchors per
+ * outer position (outer = set_n / set_inner, the reference's feature_map_size product, must be the same for all sets), the
+ * 1-based position of the set's class in class_names (each class at most once), the two thresholds. gt_boxes
+ * [batch][m][gt_ld] (device), columns 0-6 the box, column gt_ld - 1 the class id as a float; gt_ld >= 8, m <= 2048. Per frame,
+ * on the device: rows 0 .. last with a non-zero column among 0 .. gt_ld - 2 are kept (at least row 0); a kept row with class id c
+ * (truncated to int) belongs to the set of class c, and for c <= 0 of class c + num_classes -- Python's index wrap in the
+ * reference's class_names[c - 1]: an all-zero row goes to the LAST class; rows keep their order inside a set. Anchor i of set s
+ * goes to column (i / set_inner[s]) * sum(set_inner) + set_inner[0] + ... + set_inner[s - 1] + i % set_inner[s] of its frame.
+ * Outputs: labels, reg_weights, gt_ious [batch][sum(set_n)], bbox_targets [batch][sum(set_n)][7], and the state between the
+ * passes, zeroed here: gt_max_iou [batch][m] = per row the largest IoU an anchor of its set attains (0: none, or a dropped row),
+ * n_examples [batch][n_sets] = labels >= 0 per pair (the divisor under norm_by_num_examples). No workspace. */
+int cpd_anchor_assign_batch(const float *anchors, int n_sets, const int32_t set_n[], const int32_t set_inner[],
+                            const int32_t set_class[], const float set_matched[], const float set_unmatched[],
+                            int num_classes, const float *gt_boxes, int batch, int m, int gt_ld,
+                            int norm_by_num_examples, int32_t *labels, float *bbox_targets, float *reg_weights,
+                            float *gt_ious, float *gt_max_iou, int32_t *n_examples, cpd_stream_t stream);
 /* AnchorHeadTemplate.generate_predicted_boxes (anchor_head_template.py:336-383): ResidualCoder
  * decode of box_preds [batch,n,7] against anchors [n,7] plus the direction-classifier correction
  * (dir_cls_preds [batch,n,num_dir_bins] or NULL). out [batch,n,7]. */
